@@ -7,11 +7,16 @@ upsample}) over one batch of synthetic frame pairs already resident in HBM.
 Forward is embarrassingly data-parallel: ranks hold independent batches, no
 data-path collective ("scaling": "weak").
 
-Prints ONE JSON line on rank 0 (see the driver contract); extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps
+steps, writes the last step's outputs if --dump-outputs is given, and prints
+the headline line.  --full adds the extra objects:
   roofline     - the CorrBlock lookup kernel (HBM-bound), timed live with HIP
-                 events on the launch stream inside the timed region
+                 events on the launch stream inside the timed region (+ corr build,
+                 convolutions, a memory-only companion kernel, host issue time)
   cpu_baseline - the CPU oracle (a restatement of the reference pinned by golden
                  vectors; kind "port") timed on this box's host cores, rank 0, N=1 only
+  secondary    - parity, reduced precision and the other BASELINE configs (N=1,
+                 headline shape only)
 """
 import argparse
 import json
@@ -31,6 +36,7 @@ MFMA_PEAK_TFLOPS = {"f16": 2500.0, "fp32": 157.3}   # MI355X_MICROARCH.md: dense
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 # L*(2r+2)^2*s_corr (windows) + L*(2r+1)^2*4 (fp32 output) + 8 (coords); s_corr = 4 (fp32 pyramid) or 2 (fp16)
 LOOKUP_BYTES_PER_QUERY = {"fp32": 4 * 100 * 4 + 4 * 81 * 4 + 8, "fp16": 4 * 100 * 2 + 4 * 81 * 4 + 8}   # 2904 / 2104
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: all arrays of all ranks together (under 64 MB with the .npy headers)
 
 
 def cfg():
@@ -68,6 +74,29 @@ def host_cores() -> int:
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the tensors the timed path returned in its last step, one float32 DIR/<name>.npy each.  Beyond
+    `limit` bytes in all, every array keeps the same share of its elements at positions drawn from a fixed seed (the same
+    positions in every run with the same arguments), flattened in index order."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, limit / total) if total else 1.0
+    for name, a in host.items():
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * keep), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs of the last timed step -> {dirname}: {', '.join(host)}"
+        + ("" if keep == 1.0 else f" (a seeded sample of {keep:.3f} of each)"))
+
+
+def rank_suffix(world, rank):
+    """--dump-outputs file-name suffix: every rank writes its own shard's outputs when N > 1."""
+    return f"_rank{rank}" if world > 1 else ""
 
 
 def refuse_lab_switches():
@@ -277,6 +306,8 @@ def train_mode(args, world, rank, local_rank, device, ranks_seen=1):
         log(f"warm-up step {i} done")
     elapsed, loss = timed_region(step, args.steps, world, torch.cuda.synchronize, device)
     assert torch.isfinite(loss)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss" + rank_suffix(world, rank): loss}, DUMP_LIMIT_BYTES // world)
     if rank == 0:
         pairs = args.batch * world * args.steps
         print(json.dumps({
@@ -661,6 +692,101 @@ def ops_precision():
     return ops.conv_precision()
 
 
+def roofline_legs(args, model, batch, pairs_here, lk, vb, device):
+    """--full: the lookup kernel against the HBM roofline (from the dispatch-bound events of the timed region, lk / vb), its
+    memory-only companion, the corr-volume build and every convolution of one extra step against the MFMA peak."""
+    from focusflow_official_amd import ops
+    q = pairs_here * (args.height // 8) * (args.width // 8)
+    if args.graph:   # a replayed graph launches no kernels through the library: time one eager forward instead
+        ops.launch_timing_begin(ops.TIME_LOOKUP, ops.TIME_CORR_BUILD)
+        with torch.no_grad():
+            model(*batch, raft_iters=args.iters, test_mode=True)
+        lk, vb = ops.launch_timing_end(ops.TIME_LOOKUP), ops.launch_timing_end(ops.TIME_CORR_BUILD)
+    # the same launches bracketed by event pairs recorded around them (one extra untimed step): adds the dispatch gaps
+    ops.profile_begin("lookup")
+    with torch.no_grad():
+        model(*batch, raft_iters=args.iters, test_mode=True)
+    bracketed = ops.profile_end()["lookup"]
+    n_lookups = lk[0]
+    per_launch_ms = lk[1] / max(1, n_lookups) * 1e-3
+    per_q = LOOKUP_BYTES_PER_QUERY[args.pyramid]
+    # queries per LAUNCH from the launches actually seen (one lookup per iteration covers the rank's whole batch)
+    timed_steps = 1 if args.graph else args.steps
+    q = int(round(q * args.iters * timed_steps / max(1, n_lookups)))
+    achieved = per_q * q / (per_launch_ms * 1e-3) / 1e9 if per_launch_ms > 0 else 0.0
+    legs = {"roofline": {"kernel": f"lookup_dma_kernel<{'fp16' if args.pyramid == 'fp16' else 'fp32'}> (ff_corr_lookup_tiled_fwd)",
+                         "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(q, args.pyramid)[0],
+                         "traffic_source": pmc_traffic(q, args.pyramid)[1],
+                         "launches": n_lookups, "avg_launch_us": round(per_launch_ms * 1e3, 2),
+                         "min_launch_us": round(lk[2], 2), "max_launch_us": round(lk[3], 2),
+                         "timing": "HIP events bound to each dispatch of the timed region (hipExtLaunchKernelGGL start/stop events on the launching stream)",
+                         "avg_launch_us_bracketed": round(sum(bracketed) / max(1, len(bracketed)) * 1e3, 2),
+                         "algorithmic_bytes_per_query": per_q, "algorithmic_bytes_per_launch": per_q * q}}
+    if not args.graph:
+        try:
+            def one_forward():
+                with torch.no_grad():
+                    model(*batch, raft_iters=args.iters, test_mode=True)
+            mo = memory_only_companion(per_q * q, achieved, device, one_forward)
+            traffic = legs["roofline"]["traffic"]
+            if traffic and mo["bytes_per_launch"]:
+                # the same kernel's time scaled to the HBM bytes the counters see for one lookup launch (128-byte lines
+                # around 64-80-byte window rows: 1.245 x the algorithmic bytes) - a derived figure, not a measurement
+                mo["scaled_to_counted_traffic_us"] = round(mo["avg_launch_us"] * traffic / mo["bytes_per_launch"], 2)
+                mo["lookup_over_scaled"] = round(mo["scaled_to_counted_traffic_us"] / (per_launch_ms * 1e3), 4) if per_launch_ms > 0 else None
+            for key in ("in_pipeline", "in_pipeline_before_lookup", "in_pipeline_behind_flow_head"):
+                ip = mo.get(key)
+                if ip and ip.get("avg_launch_us", 0) > 0:
+                    gbs = mo["bytes_per_launch"] / (ip["avg_launch_us"] * 1e-6) / 1e9
+                    ip.update(achieved=round(gbs, 1), unit="GB/s", frac_of_peak=round(gbs / HBM_PEAK_GBS, 4), lookup_over_this=round(achieved / gbs, 4))
+                    if traffic:
+                        ip["scaled_to_counted_traffic_us"] = round(ip["avg_launch_us"] * traffic / mo["bytes_per_launch"], 2)
+                        ip["lookup_over_scaled"] = round(ip["scaled_to_counted_traffic_us"] / (per_launch_ms * 1e3), 4) if per_launch_ms > 0 else None
+            legs["roofline"]["memory_only_kernel"] = mo
+        except Exception as e:          # noqa: BLE001 - a measurement aid must not cost the bench line
+            legs["roofline"]["memory_only_kernel"] = {"error": f"{type(e).__name__}: {e}"}
+    # corr-volume build (BASELINE.md "also reported"): dense HWxC x CxHW contraction on the matrix pipe
+    q1 = (args.height // 8) * (args.width // 8)
+    vol_flop = 2.0 * pairs_here * q1 * q1 * 256
+    vol_avg_ms = vb[1] / max(1, vb[0]) * 1e-3
+    terms = {"f16x3": 3, "f16": 1, "fp32": 1}[ops.conv_precision()]
+    peak = MFMA_PEAK_TFLOPS["fp32" if ops.conv_precision() == "fp32" else "f16"]
+    issued = vol_flop * terms / (vol_avg_ms * 1e-3) / 1e12 if vol_avg_ms > 0 else 0.0
+    pyr_bytes = pairs_here * q1 * TiledPyramidBytes(args.height // 8, args.width // 8, args.pyramid == "fp16")
+    legs["roofline_corr_build"] = {
+        "kernel": "corr_build_kernel (ff_corr_build: f16x3 volume + 3 pooled levels + tiled store, one launch)" if ops.conv_precision() == "f16x3"
+                  else "conv kernel, groups=B (ff_conv2d_fwd) + pooling pass + retile", "bound": "mfma",
+        "achieved": round(issued, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(issued / peak, 4),
+        "note": f"{terms} MFMA term(s) per fp32-accurate product; useful rate {(vol_flop / (vol_avg_ms * 1e-3) / 1e12 if vol_avg_ms > 0 else 0.0):.1f} TFLOP/s; "
+                f"the launch also writes the whole pyramid once ({pyr_bytes / 1e6:.1f} MB)",
+        "write_gbs": round(pyr_bytes / (vol_avg_ms * 1e-3) / 1e9, 1) if vol_avg_ms > 0 else 0.0, "write_bytes": pyr_bytes,
+        "launches": vb[0], "avg_launch_us": round(vol_avg_ms * 1e3, 1)}
+    # all convolutions of one extra (untimed) step, each launch bracketed by HIP events: where 80 % of the step goes
+    ops.policy.single_stream = True          # bracketed launches must not overlap: this extra step runs on one stream
+    try:
+        ops.profile_begin("conv")
+        with torch.no_grad():
+            model(*batch, raft_iters=args.iters, test_mode=True)
+        conv_ms = ops.profile_end()["conv"]
+    finally:
+        ops.policy.single_stream = False
+    notes = ops.profile_notes("conv")
+    useful = sum(n[0] for n in notes)
+    issued_fl = sum(n[0] * (3 if n[1] == 1 else 1) for n in notes if n[1] != 0)
+    mfma_ms = sum(t for t, n in zip(conv_ms, notes) if n[1] != 0)
+    tot_ms = sum(conv_ms)
+    legs["roofline_conv"] = {
+        "kernel": "every ff_conv2d_fwd, ff_gru_pass and ff_fusion_pair_fwd launch of one step (conv_patch / conv_split / conv_small / conv_dma / gru_pass / fusion_pair kernels)", "bound": "mfma",
+        "achieved": round(issued_fl / (mfma_ms * 1e-3) / 1e12, 1) if mfma_ms > 0 else 0.0, "peak": MFMA_PEAK_TFLOPS["f16"],
+        "unit": "TFLOP/s", "frac": round(issued_fl / (mfma_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS["f16"], 4) if mfma_ms > 0 else 0.0,
+        "note": f"f16 MFMA FLOP issued (3 per fp32-accurate product) over the summed launch durations; useful "
+                f"{useful / (tot_ms * 1e-3) / 1e12:.1f} TFLOP/s; the f16 pipe sustains ~1600 TFLOP/s on dense data "
+                f"(tools/proto/mfma_peak.hip)",
+        "launches": len(conv_ms), "sum_launch_ms": round(tot_ms, 3), "useful_gflop_per_step": round(useful / 1e9, 1)}
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -670,9 +796,16 @@ def main():
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--iters", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="forward mode: beyond the headline line, also measure the lookup / corr-build / convolution rooflines "
+                         "(dispatch-bound events in the timed region, extra untimed steps, a memory-only companion kernel), "
+                         "the host issue time, the CPU baseline and, at N = 1 on the headline shape, the secondary configs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "forward: flow_low, flow_up; train: loss; a seeded sample beyond 60 MB; _rank<r> suffixes when N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary configs (training step, FF-PWC forward) measured after the headline at N = 1")
+                    help="--full: skip the secondary configs (training step, FF-PWC forward) measured after the headline at N = 1")
     ap.add_argument("--pyramid", choices=["fp32", "fp16"], default="fp32",
                     help="storage type of the correlation pyramid: fp32 = the reference's arithmetic (headline); fp16 = "
                          "BASELINE configs[4] (540x960 padded to 544x960, iters 32: --height 544 --width 960 --iters 32 --batch 1)")
@@ -688,6 +821,8 @@ def main():
                     help="no model: a sleep() stands in for the step so the multi-rank harness (sharding, barrier, "
                          "max-over-ranks timing, single JSON line) can be tested on CPU with gloo")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched bare (the N=1 command with a different --gpus): become the launcher; nothing above initialised HIP
         sys.exit(self_launch(args.gpus))
@@ -747,41 +882,29 @@ def main():
         step()
         torch.cuda.synchronize()
         log(f"warm-up step {i} done")
-    # HIP events bound to every lookup / corr-build dispatch of the timed region (ff_launch_timing_begin: the library hands
-    # an event pair to hipExtLaunchKernelGGL on the stream it launches on - the kernels' own execution times)
-    ops.launch_timing_begin(ops.TIME_LOOKUP, ops.TIME_CORR_BUILD)
+    # --full: HIP events bound to every lookup / corr-build dispatch of the timed region (ff_launch_timing_begin: the library
+    # hands an event pair to hipExtLaunchKernelGGL on the stream it launches on - the kernels' own execution times)
+    if args.full:
+        ops.launch_timing_begin(ops.TIME_LOOKUP, ops.TIME_CORR_BUILD)
     elapsed, out = timed_region(step, args.steps, world, torch.cuda.synchronize, device)
     log(f"{args.steps} timed steps in {elapsed:.3f} s")
-    lk, vb = ops.launch_timing_end(ops.TIME_LOOKUP), ops.launch_timing_end(ops.TIME_CORR_BUILD)
+    if args.full:
+        lk, vb = ops.launch_timing_end(ops.TIME_LOOKUP), ops.launch_timing_end(ops.TIME_CORR_BUILD)
     assert torch.isfinite(out[1]).all()
     ops.guard_check(sync=True)          # the always-on range guard looks at a forward when the next one starts: the last one here
-    # host time to issue one step, MAX over ranks like the step time itself (outside the timed region)
-    issue_ms, issue_total_ms = host_issue_time(step)
-    if world > 1:
-        t = torch.tensor([issue_ms, issue_total_ms], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        issue_ms, issue_total_ms = round(t[0].item(), 3), round(t[1].item(), 3)
+    if args.dump_outputs:
+        sfx = rank_suffix(world, rank)
+        dump_outputs(args.dump_outputs, {"flow_low" + sfx: out[0], "flow_up" + sfx: out[1]}, DUMP_LIMIT_BYTES // world)
+    if args.full:
+        # host time to issue one step, MAX over ranks like the step time itself (outside the timed region)
+        issue_ms, issue_total_ms = host_issue_time(step)
+        if world > 1:
+            t = torch.tensor([issue_ms, issue_total_ms], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            issue_ms, issue_total_ms = round(t[0].item(), 3), round(t[1].item(), 3)
 
     if rank == 0:
         pairs = args.batch * world * args.steps
-        q = (hi - lo) * (args.height // 8) * (args.width // 8)
-        if args.graph:   # a replayed graph launches no kernels through the library: time one eager forward instead
-            ops.launch_timing_begin(ops.TIME_LOOKUP, ops.TIME_CORR_BUILD)
-            with torch.no_grad():
-                model(*batch, raft_iters=args.iters, test_mode=True)
-            lk, vb = ops.launch_timing_end(ops.TIME_LOOKUP), ops.launch_timing_end(ops.TIME_CORR_BUILD)
-        # the same launches bracketed by event pairs recorded around them (one extra untimed step): adds the dispatch gaps
-        ops.profile_begin("lookup")
-        with torch.no_grad():
-            model(*batch, raft_iters=args.iters, test_mode=True)
-        bracketed = ops.profile_end()["lookup"]
-        n_lookups = lk[0]
-        per_launch_ms = lk[1] / max(1, n_lookups) * 1e-3
-        per_q = LOOKUP_BYTES_PER_QUERY[args.pyramid]
-        # queries per LAUNCH from the launches actually seen (one lookup per iteration covers the rank's whole batch)
-        timed_steps = 1 if args.graph else args.steps
-        q = int(round(q * args.iters * timed_steps / max(1, n_lookups)))
-        achieved = per_q * q / (per_launch_ms * 1e-3) / 1e9 if per_launch_ms > 0 else 0.0
         c2 = (args.height, args.width, args.iters, args.batch) == (384, 512, 12, 8) and args.pyramid == "fp32"
         line = {
             "metric": f"frame-pairs/sec FF-RAFT {args.height}x{args.width} iters={args.iters}", "value": round(pairs / elapsed, 3),
@@ -795,89 +918,21 @@ def main():
                        "parallelism": f"dp{world} (independent shards, no collective)",
                        # feature switches (A/B runs: FF_SPLIT_ACT=0, FF_GRU_PASS=0 ...) present in the environment; [] for the default line
                        "env_switches": sorted(f"{k}={v}" for k, v in os.environ.items() if k.startswith("FF_"))},
-            "roofline": {"kernel": f"lookup_dma_kernel<{'fp16' if args.pyramid == 'fp16' else 'fp32'}> (ff_corr_lookup_tiled_fwd)",
-                         "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(q, args.pyramid)[0],
-                         "traffic_source": pmc_traffic(q, args.pyramid)[1],
-                         "launches": n_lookups, "avg_launch_us": round(per_launch_ms * 1e3, 2),
-                         "min_launch_us": round(lk[2], 2), "max_launch_us": round(lk[3], 2),
-                         "timing": "HIP events bound to each dispatch of the timed region (hipExtLaunchKernelGGL start/stop events on the launching stream)",
-                         "avg_launch_us_bracketed": round(sum(bracketed) / max(1, len(bracketed)) * 1e3, 2),
-                         "algorithmic_bytes_per_query": per_q, "algorithmic_bytes_per_launch": per_q * q},
+            "rccl_ranks_seen": ranks_seen,
         }
-        if not args.graph:
-            try:
-                def one_forward():
-                    with torch.no_grad():
-                        model(*batch, raft_iters=args.iters, test_mode=True)
-                mo = memory_only_companion(per_q * q, achieved, device, one_forward)
-                traffic = line["roofline"]["traffic"]
-                if traffic and mo["bytes_per_launch"]:
-                    # the same kernel's time scaled to the HBM bytes the counters see for one lookup launch (128-byte lines
-                    # around 64-80-byte window rows: 1.245 x the algorithmic bytes) - a derived figure, not a measurement
-                    mo["scaled_to_counted_traffic_us"] = round(mo["avg_launch_us"] * traffic / mo["bytes_per_launch"], 2)
-                    mo["lookup_over_scaled"] = round(mo["scaled_to_counted_traffic_us"] / (per_launch_ms * 1e3), 4) if per_launch_ms > 0 else None
-                for key in ("in_pipeline", "in_pipeline_before_lookup", "in_pipeline_behind_flow_head"):
-                    ip = mo.get(key)
-                    if ip and ip.get("avg_launch_us", 0) > 0:
-                        gbs = mo["bytes_per_launch"] / (ip["avg_launch_us"] * 1e-6) / 1e9
-                        ip.update(achieved=round(gbs, 1), unit="GB/s", frac_of_peak=round(gbs / HBM_PEAK_GBS, 4), lookup_over_this=round(achieved / gbs, 4))
-                        if traffic:
-                            ip["scaled_to_counted_traffic_us"] = round(ip["avg_launch_us"] * traffic / mo["bytes_per_launch"], 2)
-                            ip["lookup_over_scaled"] = round(ip["scaled_to_counted_traffic_us"] / (per_launch_ms * 1e3), 4) if per_launch_ms > 0 else None
-                line["roofline"]["memory_only_kernel"] = mo
-            except Exception as e:          # noqa: BLE001 - a measurement aid must not cost the bench line
-                line["roofline"]["memory_only_kernel"] = {"error": f"{type(e).__name__}: {e}"}
-        # corr-volume build (BASELINE.md "also reported"): dense HWxC x CxHW contraction on the matrix pipe
-        q1 = (args.height // 8) * (args.width // 8)
-        vol_flop = 2.0 * (hi - lo) * q1 * q1 * 256
-        vol_avg_ms = vb[1] / max(1, vb[0]) * 1e-3
-        terms = {"f16x3": 3, "f16": 1, "fp32": 1}[ops.conv_precision()]
-        peak = MFMA_PEAK_TFLOPS["fp32" if ops.conv_precision() == "fp32" else "f16"]
-        issued = vol_flop * terms / (vol_avg_ms * 1e-3) / 1e12 if vol_avg_ms > 0 else 0.0
-        pyr_bytes = (hi - lo) * q1 * TiledPyramidBytes(args.height // 8, args.width // 8, args.pyramid == "fp16")
-        line["roofline_corr_build"] = {
-            "kernel": "corr_build_kernel (ff_corr_build: f16x3 volume + 3 pooled levels + tiled store, one launch)" if ops.conv_precision() == "f16x3"
-                      else "conv kernel, groups=B (ff_conv2d_fwd) + pooling pass + retile", "bound": "mfma",
-            "achieved": round(issued, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(issued / peak, 4),
-            "note": f"{terms} MFMA term(s) per fp32-accurate product; useful rate {(vol_flop / (vol_avg_ms * 1e-3) / 1e12 if vol_avg_ms > 0 else 0.0):.1f} TFLOP/s; "
-                    f"the launch also writes the whole pyramid once ({pyr_bytes / 1e6:.1f} MB)",
-            "write_gbs": round(pyr_bytes / (vol_avg_ms * 1e-3) / 1e9, 1) if vol_avg_ms > 0 else 0.0, "write_bytes": pyr_bytes,
-            "launches": vb[0], "avg_launch_us": round(vol_avg_ms * 1e3, 1)}
-        # all convolutions of one extra (untimed) step, each launch bracketed by HIP events: where 80 % of the step goes
-        ops.policy.single_stream = True          # bracketed launches must not overlap: this extra step runs on one stream
-        try:
-            ops.profile_begin("conv")
-            with torch.no_grad():
-                model(*batch, raft_iters=args.iters, test_mode=True)
-            conv_ms = ops.profile_end()["conv"]
-        finally:
-            ops.policy.single_stream = False
-        notes = ops.profile_notes("conv")
-        useful = sum(n[0] for n in notes)
-        issued_fl = sum(n[0] * (3 if n[1] == 1 else 1) for n in notes if n[1] != 0)
-        mfma_ms = sum(t for t, n in zip(conv_ms, notes) if n[1] != 0)
-        tot_ms = sum(conv_ms)
-        line["roofline_conv"] = {
-            "kernel": "every ff_conv2d_fwd, ff_gru_pass and ff_fusion_pair_fwd launch of one step (conv_patch / conv_split / conv_small / conv_dma / gru_pass / fusion_pair kernels)", "bound": "mfma",
-            "achieved": round(issued_fl / (mfma_ms * 1e-3) / 1e12, 1) if mfma_ms > 0 else 0.0, "peak": MFMA_PEAK_TFLOPS["f16"],
-            "unit": "TFLOP/s", "frac": round(issued_fl / (mfma_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS["f16"], 4) if mfma_ms > 0 else 0.0,
-            "note": f"f16 MFMA FLOP issued (3 per fp32-accurate product) over the summed launch durations; useful "
-                    f"{useful / (tot_ms * 1e-3) / 1e12:.1f} TFLOP/s; the f16 pipe sustains ~1600 TFLOP/s on dense data "
-                    f"(tools/proto/mfma_peak.hip)",
-            "launches": len(conv_ms), "sum_launch_ms": round(tot_ms, 3), "useful_gflop_per_step": round(useful / 1e9, 1)}
-        line["rccl_ranks_seen"] = ranks_seen
-        line["host"] = {"host_issue_ms": issue_ms, "step_ms_same_sample": issue_total_ms, "threads_per_rank": host_threads, "cores": host_cores(),
-                        "note": "median host time to issue one step with an empty queue (no sync inside) and the wall time of the same step, "
-                                "MAX over ranks; a rank is host-bound where the two meet"}
-        checker = {}
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args.height, args.width, args.iters, keep=checker)
-        if world == 1 and c2 and not args.no_secondary and not args.graph:
-            step = model = batch = None          # noqa: F841 - release the forward model before the secondary configs
-            torch.cuda.empty_cache()
-            line["secondary"] = parity_and_reduced_precision(args, device, checker)
-            line["secondary"].update(secondary_measurements(args, device))
+        if args.full:
+            line.update(roofline_legs(args, model, batch, hi - lo, lk, vb, device))
+            line["host"] = {"host_issue_ms": issue_ms, "step_ms_same_sample": issue_total_ms, "threads_per_rank": host_threads, "cores": host_cores(),
+                            "note": "median host time to issue one step with an empty queue (no sync inside) and the wall time of the same step, "
+                                    "MAX over ranks; a rank is host-bound where the two meet"}
+            checker = {}
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args.height, args.width, args.iters, keep=checker)
+            if world == 1 and c2 and not args.no_secondary and not args.graph:
+                step = model = batch = None          # noqa: F841 - release the forward model before the secondary configs
+                torch.cuda.empty_cache()
+                line["secondary"] = parity_and_reduced_precision(args, device, checker)
+                line["secondary"].update(secondary_measurements(args, device))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

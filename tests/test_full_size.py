@@ -15,6 +15,14 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+@pytest.fixture(autouse=True)
+def restore_threads():
+    """Two tests here raise torch's thread count for their CPU oracle runs: give the later tests of the session theirs back."""
+    prev = torch.get_num_threads()
+    yield
+    torch.set_num_threads(prev)
+
+
 def test_config3_training_step_8x368x496_it12(det_sd):
     from focusflow_official_amd import FF_RAFT_FUSION
     from focusflow_official_amd.losses import build_losses

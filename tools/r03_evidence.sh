@@ -5,11 +5,11 @@ set -u
 out=$PWD/gpurun_out/r03
 mkdir -p "$out"
 export PYTHONUNBUFFERED=1
-echo "== default bench line"; python bench.py > "$out/bench_line.json" 2> "$out/bench_line.err"; tail -c 400 "$out/bench_line.json"
+echo "== bench line with every leg (--full)"; python bench.py --full > "$out/bench_line.json" 2> "$out/bench_line.err"; tail -c 400 "$out/bench_line.json"
 echo "== kernel trace of the bench command"
-bash tools/prof_trace.sh r03/bench_b8 bench.py --no-secondary --no-cpu-baseline
+bash tools/prof_trace.sh r03/bench_b8 bench.py --full --no-secondary --no-cpu-baseline
 echo "== counter passes of the bench command"
-PASSES="1 2 4 6 7" bash tools/prof_pmc.sh r03/bench_pmc bench.py --steps 5 --warmup 2 --no-secondary --no-cpu-baseline > "$out/bench_pmc.log" 2>&1
+PASSES="1 2 4 6 7" bash tools/prof_pmc.sh r03/bench_pmc bench.py --steps 5 --warmup 2 --full --no-secondary --no-cpu-baseline > "$out/bench_pmc.log" 2>&1
 echo "== training step"
 python bench.py --mode train --steps 6 --warmup 3 > "$out/train_line.json" 2> "$out/train_line.err"
 bash tools/prof_trace.sh r03/train_b8 bench.py --mode train --steps 4 --warmup 2

@@ -5,7 +5,7 @@ set -u
 out=$PWD/gpurun_out
 root=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$out/tve.trace" -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 10 --warmup 3 --no-secondary --no-cpu-baseline > "$out/tve.log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$out/tve.trace" -- python3 "$root/bench.py" --steps 10 --warmup 3 --full --no-secondary --no-cpu-baseline > "$out/tve.log" 2>&1
 f=$(find "$out/tve.trace" -name "*kernel_trace.csv" | head -1)
 python3 - "$f" "$out/tve.log" > "$out/trace_vs_events.txt" <<'P'
 import csv, json, sys
