@@ -66,12 +66,18 @@ class CorrBlock:
     def __call__(self, coords: torch.Tensor, want_taps: bool = False):
         if self._chunks is not None:
             assert not want_taps, "taps of a chunked CorrBlock: ask the chunks"
-            if self._padded is None:
-                b, h, w, _ = coords.shape
-                self._padded = torch.zeros((b, h, w, (self._nk + 31) // 32 * 32), dtype=torch.float32, device=coords.device)
+            b, h, w, _ = coords.shape
+            if torch.is_grad_enabled():
+                # a recorded pass (frozen encoders: the volume is not differentiated, but convc1 saves its input for its weight
+                # gradient): a fresh tensor per call - the shared buffer would be overwritten by the next iteration's lookup
+                out = ops.empty_nhwc(b, h, w, self._nk, coords)
+            else:
+                if self._padded is None:
+                    self._padded = torch.zeros((b, h, w, (self._nk + 31) // 32 * 32), dtype=torch.float32, device=coords.device)
+                out = self._padded
             for lo, hi, blk in self._chunks:
-                ops.corr_lookup_tiled(blk.pyr, coords[lo:hi], out=self._padded[lo:hi][..., :self._nk])
-            return self._padded
+                ops.corr_lookup_tiled(blk.pyr, coords[lo:hi], out=out[lo:hi][..., :self._nk])
+            return out
         if self._token is not None and not want_taps:
             return fn.LookupFn.apply(self._token, self, coords)
         if want_taps or torch.is_grad_enabled():

@@ -96,14 +96,8 @@ class RAFT(nn.Module):
         # encoder, whose InstanceNorm statistics / apply passes are memory-bound - the two use different parts of the chip.
         # recorded passes: the whole update loop is one autograd node (train_loop.UpdateLoopFn); its parameters' gradients leave
         # through a gate node created HERE, before the encoders, so that its backward runs after theirs (train_loop.LoopParamGate)
-        fused_train = (torch.is_grad_enabled() and train_loop.ENABLED and _GRU_CTX_ONCE and ops.w_format() in (_hip.W_F16X3, _hip.W_F16)
-                       and not test_mode)
-        loop_gate = None
-        if fused_train and train_loop.defer_param_grads():
-            lp = train_loop.loop_params(self.update_block)
-            if all(q is None or q.is_cuda for q in lp) and any(q is not None and q.requires_grad for q in lp):
-                box = {}
-                loop_gate = (box, train_loop.LoopParamGate.apply(box, *lp))
+        fused_train = self._fused_train(test_mode)
+        loop_gate = self._loop_gate(fused_train)
         ops.policy.encoder_streams_ok = b * hh * ww >= _STREAMS_MIN_PIXELS
         two_streams = (_ENC_STREAMS and ops.policy.encoder_streams_ok and not ops.policy.single_stream and (not torch.is_grad_enabled() or train_streams())
                        )      # (also while a hipGraph is being captured: one level of forks is capturable; the branch forks inside each encoder are not - cce._branches)
@@ -123,11 +117,7 @@ class RAFT(nn.Module):
         f12 = self.fnet(ops.cat_batch(image1, image2), ops.cat_batch(mask1, mask2))
         fmap1, fmap2 = f12[:b], f12[b:]
         self.fmap = fmap1
-        # the fused update-loop node takes the feature maps themselves - the pyramid is then built outside the tape
-        if fused_train:
-            corr_fn = CorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
-        else:
-            corr_fn = CorrBlock(fmap1, fmap2, radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
+        corr_fn = self._corr_block(fmap1, fmap2, fused_train)      # (before the context encoder's join: it overlaps that stream)
         if two_streams:
             main.wait_event(join)
             cnet.record_stream(main)
@@ -164,6 +154,39 @@ class RAFT(nn.Module):
             ops.act_copy(cnet[..., :128], net, ACT_TANH)
             ops.act_copy(cnet[..., 128:], inp, ACT_RELU)
         coords1 = ops.coords_init(b, h8, w8, cnet, flow_init)      # never differentiated (raft.py:216)
+        return self._update_loop(net, inp, fmap1, fmap2, coords1, iters, loop_gate, corr_fn, test_mode)
+
+    def _fused_train(self, test_mode=False) -> bool:
+        """Whether this pass records the update loop as ONE autograd node (train_loop.UpdateLoopFn) when it is eligible."""
+        return (torch.is_grad_enabled() and train_loop.ENABLED and _GRU_CTX_ONCE and ops.w_format() in (_hip.W_F16X3, _hip.W_F16)
+                and not test_mode)
+
+    def _loop_gate(self, fused_train):
+        """(box, token) of a train_loop.LoopParamGate over the update block's parameters, or None."""
+        if fused_train and train_loop.defer_param_grads():
+            lp = train_loop.loop_params(self.update_block)
+            if all(q is None or q.is_cuda for q in lp) and any(q is not None and q.requires_grad for q in lp):
+                box = {}
+                return box, train_loop.LoopParamGate.apply(box, *lp)
+        return None
+
+    def _corr_block(self, fmap1, fmap2, fused_train):
+        # the fused update-loop node takes the feature maps themselves - the pyramid is then built outside the tape
+        if fused_train:
+            return CorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
+        return CorrBlock(fmap1, fmap2, radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
+
+    def _update_loop(self, net, inp, fmap1, fmap2, coords1, iters, loop_gate=None, corr_fn=None, test_mode=False):
+        """Everything after the encoders (raft.py:199-236): the correlation block (unless the caller built it already),
+        the context share of the GRU gates, and the iterations - through the fused node (train_loop.UpdateLoopFn) where
+        it is eligible, the per-operation tape or the inference loop otherwise.  net / inp: the activated context
+        features (NHWC); loop_gate: (box, token) of the LoopParamGate created before the encoders, or None.  Returns the
+        list of up-sampled flows, or (flow_low, flow_up) in test_mode."""
+        b, h8, w8, _ = net.shape
+        fused_train = self._fused_train(test_mode)
+        if corr_fn is None:
+            corr_fn = self._corr_block(fmap1, fmap2, fused_train)
+        taped = fn.recording(net, inp)
         # the context features' share of the GRU gate convolutions does not change over the iterations
         gru_pre = self.update_block.gru.prepare(inp, exact=self._exact_ctx and not taped) if _GRU_CTX_ONCE and (taped or fused_train or not torch.is_grad_enabled()) else None
         if fused_train:

@@ -83,6 +83,22 @@ class LoopParamGate(torch.autograd.Function):
         return (None, *_unpack_param_grads(convs, acc, lambda j: need[1 + j]))
 
 
+def _tensors(obj):
+    """The distinct storages among the tensors in nested dicts / lists / tuples (one base tensor each)."""
+    seen = {}
+    todo = [obj]
+    while todo:
+        o = todo.pop()
+        if isinstance(o, torch.Tensor):
+            base = o if o._base is None else o._base
+            seen.setdefault(id(base), base)
+        elif isinstance(o, dict):
+            todo += o.values()
+        elif isinstance(o, (list, tuple)):
+            todo += o
+    return list(seen.values())
+
+
 def _side_stream(device):
     key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
     if key not in _side_streams:
@@ -423,6 +439,11 @@ class UpdateLoopFn(torch.autograd.Function):
             if side is not main:
                 ev = torch.cuda.Event()
                 ev.record(side)
+                # torch.autograd.grad / backward(inputs=...) that leave out the loop's parameters prune the gate: nothing then waits
+                # for the event, and the graph frees the mailbox with this pass - the buffers the slabs read and write must not go
+                # back to the allocator before the side stream is through with them
+                for t in _tensors((S, G, words, acc)):
+                    t.record_stream(side)
             # (the stacks the slabs read were allocated on the main stream: they stay referenced until the gate has waited for the
             # event, or the allocator would hand their memory to the encoders' backward while the side stream still reads it)
             ctx.box["job"] = (convs, acc, ev, (S, G, words))

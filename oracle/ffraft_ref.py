@@ -332,22 +332,28 @@ def raft_forward(sd: Dict[str, Tensor], image1, image2, mask1, mask2, iters=12,
         coords1 = coords1 + flow_init
     if taps is not None:
         taps.update(fmap1=fmap1, fmap2=fmap2, cnet=cnet, pyramid=pyramid, iters=[])
+    preds, coords1 = update_loop(sd, p + "update_block", pyramid, net, inp, coords0, coords1, iters, taps)
+    if test_mode:
+        return coords1 - coords0, preds[-1] if preds else None
+    return preds
+
+
+def update_loop(sd, p, pyramid, net, inp, coords0, coords1, iters, taps: Optional[dict] = None):
+    """raft.py:218-231: `iters` x {lookup, update block, coordinate step, convex up-sampling}; p = the update block's
+    prefix.  The coordinates are never differentiated (raft.py:220).  Returns (the up-sampled flows, coords1)."""
     preds = []
-    flow_up = None
     for _ in range(iters):
         coords1 = coords1.detach()
         corr = corr_lookup(pyramid, coords1)
         flow = coords1 - coords0
-        net, up_mask, delta = update_block(sd, p + "update_block", net, inp, corr, flow)
+        net, up_mask, delta = update_block(sd, p, net, inp, corr, flow)
         coords1 = coords1 + delta
         flow_up = upsample_flow(coords1 - coords0, up_mask)
         preds.append(flow_up)
         if taps is not None:
             taps["iters"].append(dict(corr=corr, net=net, up_mask=up_mask, delta=delta,
                                       coords1=coords1, flow_up=flow_up))
-    if test_mode:
-        return coords1 - coords0, flow_up
-    return preds
+    return preds, coords1
 
 
 def ffraft_forward(sd, image1, image2, mask1, mask2=None, raft_iters=12, flow_init=None,
