@@ -1,1 +1,1 @@
-from focusflow_official_amd.corr_block import CorrBlock  # noqa: F401
+from focusflow_official_amd.corr_block import AlternateCorrBlock, CorrBlock  # noqa: F401

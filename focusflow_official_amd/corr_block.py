@@ -1,14 +1,24 @@
 """CorrBlock on the HIP path (corr.py:12-60): all-pairs volume on the f16 matrix pipe (fp16-split operands, fp32-level
 accuracy) with the 4-level average-pool pyramid written once from the accumulators in a tiled HBM layout, and the
 radius-4 bilinear window lookup over that layout."""
+import functools
 import os
 
 import torch
 
-from . import fn, ops
+from . import _hip, fn, ops
 
 PYRAMID_DTYPES = ("fp32", "fp16")
 _MAX_PYRAMID_BYTES = int(os.environ.get("FF_MAX_PYRAMID_BYTES", str(3900 * 1000 * 1000)))      # (tests lower it to exercise the chunking)
+_LOOKUP_SPAN = 0xfff00000      # csrc/corr_lookup_dma.hip: the four levels of a lookup lie within this many bytes (one buffer resource)
+
+
+@functools.lru_cache(maxsize=64)
+def pyramid_span(h: int, w: int, half: bool, pairs: int = 1) -> int:
+    """Bytes from the first to the last element of the four levels of `pairs` pyramids as ops.TiledPyramid.empty lays them out."""
+    esz = 2 if half else 4
+    n = [pairs * h * w * ops.TiledPyramid.plane_elems(h, w, l, half) for l in range(4)]
+    return sum((x * esz + 255) // 256 * 256 for x in n[:3]) + n[3] * esz
 
 
 class CorrBlock:
@@ -38,6 +48,14 @@ class CorrBlock:
         # in batch chunks, each with its own allocation (inference; a recorded pass keeps one pyramid for its backward).
         self._chunks = None
         b, h, w, _ = fmap1.shape
+        if fmap1.is_cuda and pyramid_span(h, w, self.half) >= _LOOKUP_SPAN:
+            # refused before the pyramid is allocated and built (the lookup would refuse it afterwards)
+            fits16 = not self.half and pyramid_span(h, w, True) < _LOOKUP_SPAN
+            raise _hip.FocusFlowHipError(
+                f"CorrBlock: the {pyramid_dtype} correlation pyramid of ONE pair at {h}x{w} (1/8 resolution) spans "
+                f"{pyramid_span(h, w, self.half) / 1e9:.2f} GB; the lookup addresses a pyramid through one 4 GB buffer resource.  "
+                "Use alternate_corr=True (on-the-fly correlation, memory linear in the image area)"
+                + (', or corr_pyramid_dtype="fp16" (its pyramid fits)' if fits16 else "") + ".")
         per_pair = h * w * sum(ops.TiledPyramid.plane_elems(h, w, l, self.half) for l in range(4)) * (2 if self.half else 4) if fmap1.is_cuda else 0
         if per_pair * b >= _MAX_PYRAMID_BYTES and b > 1 and not fn.recording(fmap1, fmap2):
             per = max(1, _MAX_PYRAMID_BYTES // per_pair)
@@ -86,4 +104,41 @@ class CorrBlock:
             b, h, w, _ = coords.shape
             self._padded = torch.zeros((b, h, w, (self._nk + 31) // 32 * 32), dtype=torch.float32, device=coords.device)
         ops.corr_lookup_tiled(self.pyr, coords, out=self._padded[..., :self._nk])
+        return self._padded
+
+
+class AlternateCorrBlock:
+    """The reference's AlternateCorrBlock (FF_RAFT_Core/corr.py:63-91): CorrBlock's numbers (up to the order of the
+    dot-product sums; the taps are bit-identical) without the all-pairs pyramid - memory linear in the image area, so a
+    1088x1920 pair runs in fp32 and 2160x3840 at all.  Same call protocol as CorrBlock: NHWC fmaps (B, H8, W8, 256) fp32,
+    ``__call__(coords, want_taps=False)`` with NHWC [x, y] coordinates -> NHWC (B, H8, W8, 324).
+
+    Construction pools fmap2 once (ops.corr_alt_prepare); every call computes, per tile of queries, the dot products of
+    the union of their windows on the matrix pipe and blends them (ops.corr_alt_lookup).  Inference only: there is no
+    backward, so the feature maps must not be recorded (RAFT keeps the materialised pyramid for recorded passes).
+    ``corr_pyramid_dtype`` does not apply (nothing is stored per pair of positions); the arithmetic follows
+    FF_CONV_PRECISION: three-term split f16 products, or exact fp32 ones under "fp32".  ``pyr`` is None (the fused
+    training node declines the block)."""
+
+    def __init__(self, fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: int = 4, radius: int = 4):
+        if num_levels != 4 or radius != 4:
+            raise NotImplementedError("the on-the-fly correlation kernels are built for 4 levels, radius 4 (all reference configs)")
+        if fn.recording(fmap1, fmap2):
+            raise _hip.FocusFlowHipError("AlternateCorrBlock has no backward: build it from feature maps that are not recorded "
+                                         "(torch.no_grad() or detached / frozen encoders)")
+        self.num_levels, self.radius = num_levels, radius
+        self.pyr = None
+        self._ops = ops.corr_alt_prepare(fmap1.contiguous(), fmap2.contiguous())
+        self._nk = num_levels * (2 * radius + 1) ** 2
+        self._padded = None
+
+    def __call__(self, coords: torch.Tensor, want_taps: bool = False):
+        if want_taps or torch.is_grad_enabled():
+            # (a recorded update block saves its input: a fresh tensor per call)
+            return ops.corr_alt_lookup(self._ops, coords, want_taps)
+        if self._padded is None:
+            # the 352-channel buffer of CorrBlock (pad channels zero once, reused by every iteration of this pair)
+            b, h, w, _ = coords.shape
+            self._padded = torch.zeros((b, h, w, (self._nk + 31) // 32 * 32), dtype=torch.float32, device=coords.device)
+        ops.corr_alt_lookup(self._ops, coords, out=self._padded[..., :self._nk])
         return self._padded

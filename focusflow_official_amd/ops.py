@@ -445,6 +445,60 @@ def corr_lookup_tiled(pyr: TiledPyramid, coords: Tensor, want_taps: bool = False
     return (out, taps) if want_taps else out
 
 
+class AltOperands:
+    """What ff_corr_alt_prepare leaves for the on-the-fly lookup (AlternateCorrBlock): the operand rows of fmap1 and of the
+    four levels of fmap2 (split pairs, or fp32 rows with levels 0 = fmap2 itself).  Memory linear in the image area."""
+    __slots__ = ("f1", "levels", "split", "b", "h0", "w0", "_keep")
+
+    def ptrs(self):
+        return (C.c_void_p * 4)(*[lv.data_ptr() for lv in self.levels])
+
+
+TIME_ALT_LOOKUP, TIME_ALT_PREPARE = 4, 5                  # include/focusflow_hip.h: FF_TIME_*
+
+
+def corr_alt_prepare(fmap1: Tensor, fmap2: Tensor) -> AltOperands:
+    """AlternateCorrBlock.__init__: pooled levels 1-3 of fmap2 and the operand form of the lookup (ff_corr_alt_prepare), one
+    launch.  The split precisions get fp16 split pairs of fmap1 and of every level; the exact-fp32 one fp32 rows of levels 1-3."""
+    b, h, w, c = fmap1.shape
+    _require_gpu(fmap1)
+    _require_gpu(fmap2)
+    assert fmap1.is_contiguous() and fmap2.is_contiguous() and fmap2.shape == fmap1.shape
+    if c != 256:
+        raise _hip.FocusFlowHipError(f"corr_alt_prepare: {c} feature channels (the kernels are built for 256)")
+    split = w_format() != _hip.W_F32
+    rows = [b * (h >> l) * (w >> l) for l in range(4)]
+    first = 0 if split else 1
+    flat = torch.empty((sum(rows[first:]) + (b * h * w if split else 0)) * 256, dtype=torch.float32, device=fmap1.device)
+    views, o = [], 0
+    for l in range(first, 4):
+        views.append(flat[o * 256:(o + rows[l]) * 256].view(rows[l], 256))
+        o += rows[l]
+    levels = views if split else [fmap2.view(rows[0], 256)] + views
+    f1 = flat[o * 256:].view(b * h * w, 256) if split else fmap1.view(b * h * w, 256)
+    ops = AltOperands()
+    ops.f1, ops.levels, ops.split, ops.b, ops.h0, ops.w0, ops._keep = f1, levels, split, b, h, w, (fmap1, fmap2, flat)
+    lv = (C.c_void_p * 4)(*[(x.data_ptr() if (split or l > 0) else 0) for l, x in enumerate(levels)])
+    _timed_call("corr_alt_prepare", "ff_corr_alt_prepare", _p(fmap1), _p(fmap2), b, h, w, c, int(split), _p(f1) if split else C.c_void_p(0),
+                lv, _stream())
+    return ops
+
+
+def corr_alt_lookup(ops: AltOperands, coords: Tensor, want_taps: bool = False, out: Optional[Tensor] = None):
+    """AlternateCorrBlock.__call__ (ff_corr_alt_lookup): coords (B, H, W, 2) [x, y] -> (B, H, W, 324) (+ int32 taps
+    (B*H*W, 4, 2, 9), bit-identical to corr_lookup_tiled's).  `out`: a (B,H,W,324) view of a wider buffer."""
+    _require_gpu(coords)
+    b, h, w, _ = coords.shape
+    assert coords.is_contiguous() and (b, h, w) == (ops.b, ops.h0, ops.w0)
+    if out is None:
+        out = empty_nhwc(b, h, w, 324, coords)
+    assert out.shape == (b, h, w, 324)
+    taps = torch.empty((b * h * w, 4, 2, 9), dtype=torch.int32, device=coords.device) if want_taps else None
+    _timed_call("lookup", "ff_corr_alt_lookup", _p(ops.f1), ops.ptrs(), int(ops.split), _p(coords), b, h, w, _p(out), _ld(out),
+                _p(taps), _stream())
+    return (out, taps) if want_taps else out
+
+
 def corr_volume(fmap1: Tensor, fmap2: Tensor) -> Tensor:
     """corr.py:52-60: vol[b][i][j] = <f1[b,i,:], f2[b,j,:]> / sqrt(C) as a grouped 1x1 conv
     whose per-sample weights are fmap2.  Returns (B, Q, Q) planes [B*Q][H8][W8]."""

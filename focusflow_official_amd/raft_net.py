@@ -6,7 +6,7 @@ import torch.nn as nn
 
 from . import _hip, cce, fn, ops, train_loop
 from .cce import BasicParallelFusionLayer, train_streams
-from .corr_block import CorrBlock
+from .corr_block import AlternateCorrBlock, CorrBlock
 from .ops import ACT_RELU, ACT_TANH
 from .update_block import BasicUpdateBlock, split_activations
 
@@ -30,14 +30,11 @@ class RAFT(nn.Module):
         self.context_dim = cdim = 128
         self.corr_levels, self.corr_radius = 4, 4
         self.dropout = dropout
-        # ALT_CORR selects an on-the-fly correlation in the reference (its alt_cuda_corr extension is not vendored
-        # there, corr.py:5-9); here the materialised pyramid is always used - say so, the caller may have set the flag to
-        # bound memory (B * Q^2 * 5.3 bytes in fp32, half that with corr_pyramid_dtype = "fp16")
+        # ALT_CORR selects the on-the-fly correlation (corr_block.AlternateCorrBlock: memory linear in the image area instead
+        # of B * Q^2 * 5.3 bytes) wherever the feature maps are not recorded - inference, frozen encoders; a pass that records
+        # them keeps the materialised pyramid, whose backward exists (_corr_block)
         self.alternate_corr = alternate_corr
-        if alternate_corr:
-            import warnings
-            warnings.warn("alternate_corr=True: the HIP path has no on-the-fly correlation; the materialised all-pairs "
-                          "pyramid is used (O((H*W/64)^2) memory per pair; corr_pyramid_dtype='fp16' halves it)")
+        self._alt_warned = False
         # storage type of the correlation pyramid: None = $FF_CORR_PYRAMID or "fp32"; "fp16" = BASELINE configs[4]
         self.corr_pyramid_dtype = None
         mc = cfg.TRAIN.MASK_CHANNEL
@@ -171,6 +168,14 @@ class RAFT(nn.Module):
         return None
 
     def _corr_block(self, fmap1, fmap2, fused_train):
+        if self.alternate_corr:
+            if not fn.recording(fmap1, fmap2):
+                return AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
+            if not self._alt_warned:
+                import warnings
+                warnings.warn("alternate_corr=True: the feature maps are recorded (trained encoders), and the on-the-fly "
+                              "correlation has no backward - this model's recorded passes use the materialised all-pairs pyramid")
+                self._alt_warned = True
         # the fused update-loop node takes the feature maps themselves - the pyramid is then built outside the tape
         if fused_train:
             return CorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)

@@ -70,7 +70,9 @@ int ff_abi_version(void);
 #define FF_TIME_LOOKUP 1        /* ff_corr_lookup_tiled_fwd's kernel */
 #define FF_TIME_CORR_BUILD 2    /* ff_corr_build's kernel            */
 #define FF_TIME_PROBE 3         /* ff_probe_memory_kernel's kernel   */
-#define FF_TIME_KINDS 3
+#define FF_TIME_ALT_LOOKUP 4    /* ff_corr_alt_lookup's kernel       */
+#define FF_TIME_ALT_PREPARE 5   /* ff_corr_alt_prepare's kernel      */
+#define FF_TIME_KINDS 5
 int ff_launch_timing_begin(int which);
 int ff_launch_timing_end(int which, long long* launches, double* total_us, double* min_us, double* max_us);
 /* Measurement aid (probe.hip): a memory-only kernel with the lookup's launch shape (`blocks` one-wave blocks) and access
@@ -301,6 +303,26 @@ int ff_corr_lookup_tiled_bwd_all(float* d0, const float* const* coords_list, con
                                  long long queries, int h0, int w0, void* stream);
 int ff_corr_pyramid_tiled_bwd(float* d0, float* d1, float* d2, const float* d3, long long planes, int h0, int w0,
                               void* stream);
+
+/* ------------------------------------------------------------------------
+ * AlternateCorrBlock (FF_RAFT_Core/corr.py:63-91): CorrBlock.__call__'s numbers without the all-pairs pyramid (memory
+ * linear in the image area; inference only - there is no backward).  fmap1 / fmap2: NHWC [B][h0][w0][C] fp32, C = 256.
+ *   ff_corr_alt_prepare  once per pair of feature maps: pooled levels 1-3 of fmap2 (avg_pool2d(2, 2), floor semantics)
+ *                        in the lookup's operand form.  split != 0 (the fp16-split precisions): f1_split [B*Q][1024 B] and
+ *                        levels[0..3] [B*h_l*w_l][1024 B] receive split pairs in ff_pack_split_f16's row format.  split == 0
+ *                        (exact fp32): levels[1..3] receive fp32 rows [B*h_l*w_l][C]; f1_split and levels[0] are not used.
+ *   ff_corr_alt_lookup   per iteration: out NHWC [B*Q][out_ld] (channels 0..323, k = level*81 + a*9 + b, a = x-offset
+ *                        index, as ff_corr_lookup_tiled_fwd), taps (optional) int32 [B*Q][4][2][9] bit-identical to
+ *                        ff_corr_lookup_tiled_fwd's.  f1 / levels: split != 0: what ff_corr_alt_prepare wrote; split == 0:
+ *                        fmap1, {fmap2, levels[1..3]}.  Products on the matrix pipe: three-term split f16 or exact fp32.
+ *                        Coordinate-dependent routes are chosen on the device; nothing is allocated, nothing waits for
+ *                        the host (capturable).  Level 3 must be at least 2x2 (the sampler divides by n - 1).
+ * ---------------------------------------------------------------------- */
+int ff_corr_alt_prepare(const float* fmap1, const float* fmap2, int B, int h0, int w0, int C, int split, void* f1_split,
+                        void* const* levels /* HOST array of 4 device ptrs */, void* stream);
+int ff_corr_alt_lookup(const void* f1, const void* const* levels /* HOST array of 4 device ptrs */, int split,
+                       const float* coords /* [B*Q][2] x,y */, int B, int h0, int w0, float* out, int out_ld, int* taps,
+                       void* stream);
 
 /* ------------------------------------------------------------------------
  * Update-block glue (raft.py:205-231, update.py:45-60).
