@@ -100,6 +100,8 @@ _SIGS = {
     "ff_corr_pyramid_tiled_bwd": [_fp, _fp, _fp, _fp, _ll, C.c_int, C.c_int, _fp],
     "ff_corr_alt_prepare": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(_fp), _fp],
     "ff_corr_alt_lookup": [_fp, C.POINTER(_fp), C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp],
+    "ff_corr_alt_lookup_bwd": [_fp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp,
+                               C.POINTER(_fp), _fp],
     "ff_act_copy": [_fp, C.c_int, _fp, C.c_int, _ll, C.c_int, C.c_int, _fp],
     "ff_range_probe": [_fp, C.c_int, _ll, C.c_int, _fp, _fp],
     "ff_split_copy": [_fp, C.c_int, _fp, C.c_int, _ll, C.c_int, C.c_int, C.c_int, _fp],

@@ -21,6 +21,18 @@ def pyramid_span(h: int, w: int, half: bool, pairs: int = 1) -> int:
     return sum((x * esz + 255) // 256 * 256 for x in n[:3]) + n[3] * esz
 
 
+def pyramid_bytes(b: int, h: int, w: int, half: bool) -> int:
+    """Bytes of the materialised pyramid of a batch of b pairs at h x w (1/8 resolution)."""
+    return b * h * w * sum(ops.TiledPyramid.plane_elems(h, w, l, half) for l in range(4)) * (2 if half else 4)
+
+
+def pyramid_fits(b: int, h: int, w: int, pyramid_dtype: str = None) -> bool:
+    """Whether a RECORDED pass can materialise the batch's pyramid: one allocation under _MAX_PYRAMID_BYTES (a recorded
+    pass keeps one pyramid for its backward) and one pair within the lookup's buffer resource."""
+    half = (pyramid_dtype or os.environ.get("FF_CORR_PYRAMID", "fp32")) == "fp16"
+    return pyramid_bytes(b, h, w, half) < _MAX_PYRAMID_BYTES and pyramid_span(h, w, half) < _LOOKUP_SPAN
+
+
 class CorrBlock:
     """Same call protocol as the reference: build once per pair, call per iteration.
 
@@ -56,7 +68,7 @@ class CorrBlock:
                 f"{pyramid_span(h, w, self.half) / 1e9:.2f} GB; the lookup addresses a pyramid through one 4 GB buffer resource.  "
                 "Use alternate_corr=True (on-the-fly correlation, memory linear in the image area)"
                 + (', or corr_pyramid_dtype="fp16" (its pyramid fits)' if fits16 else "") + ".")
-        per_pair = h * w * sum(ops.TiledPyramid.plane_elems(h, w, l, self.half) for l in range(4)) * (2 if self.half else 4) if fmap1.is_cuda else 0
+        per_pair = pyramid_bytes(1, h, w, self.half) if fmap1.is_cuda else 0
         if per_pair * b >= _MAX_PYRAMID_BYTES and b > 1 and not fn.recording(fmap1, fmap2):
             per = max(1, _MAX_PYRAMID_BYTES // per_pair)
             self._chunks = [(lo, min(b, lo + per), CorrBlock(fmap1[lo:lo + per], fmap2[lo:lo + per], num_levels, radius, pyramid_dtype))
@@ -114,25 +126,29 @@ class AlternateCorrBlock:
     ``__call__(coords, want_taps=False)`` with NHWC [x, y] coordinates -> NHWC (B, H8, W8, 324).
 
     Construction pools fmap2 once (ops.corr_alt_prepare); every call computes, per tile of queries, the dot products of
-    the union of their windows on the matrix pipe and blends them (ops.corr_alt_lookup).  Inference only: there is no
-    backward, so the feature maps must not be recorded (RAFT keeps the materialised pyramid for recorded passes).
-    ``corr_pyramid_dtype`` does not apply (nothing is stored per pair of positions); the arithmetic follows
-    FF_CONV_PRECISION: three-term split f16 products, or exact fp32 ones under "fp32".  ``pyr`` is None (the fused
-    training node declines the block)."""
+    the union of their windows on the matrix pipe and blends them (ops.corr_alt_lookup).  Recorded feature maps: the
+    construction is an autograd node (fn.AltCorrBuildFn) whose backward runs the backward of all of the pass's lookups in
+    one launch (ops.corr_alt_lookup_bwd: exact fp32 in every precision), every call a fresh tensor (fn.AltLookupFn).
+    ``corr_pyramid_dtype`` does not apply (nothing is stored per pair of positions); the lookup's arithmetic follows
+    FF_CONV_PRECISION: three-term split f16 products, or exact fp32 ones under "fp32".  ``pyr`` is None; the fused
+    training node (train_loop.UpdateLoopFn) takes the block through ``_ops``."""
 
     def __init__(self, fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: int = 4, radius: int = 4):
         if num_levels != 4 or radius != 4:
             raise NotImplementedError("the on-the-fly correlation kernels are built for 4 levels, radius 4 (all reference configs)")
-        if fn.recording(fmap1, fmap2):
-            raise _hip.FocusFlowHipError("AlternateCorrBlock has no backward: build it from feature maps that are not recorded "
-                                         "(torch.no_grad() or detached / frozen encoders)")
         self.num_levels, self.radius = num_levels, radius
         self.pyr = None
-        self._ops = ops.corr_alt_prepare(fmap1.contiguous(), fmap2.contiguous())
+        self._token = None
+        if fn.recording(fmap1, fmap2):
+            self._token = fn.AltCorrBuildFn.apply(fmap1.contiguous(), fmap2.contiguous(), self)      # sets self._ops
+        else:
+            self._ops = ops.corr_alt_prepare(fmap1.contiguous(), fmap2.contiguous())
         self._nk = num_levels * (2 * radius + 1) ** 2
         self._padded = None
 
     def __call__(self, coords: torch.Tensor, want_taps: bool = False):
+        if self._token is not None and not want_taps:
+            return fn.AltLookupFn.apply(self._token, self, coords)
         if want_taps or torch.is_grad_enabled():
             # (a recorded update block saves its input: a fresh tensor per call)
             return ops.corr_alt_lookup(self._ops, coords, want_taps)

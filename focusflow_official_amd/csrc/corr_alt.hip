@@ -21,6 +21,7 @@
 #pragma clang fp contract(off)
 #include <cstdint>
 #include "ff_common.h"
+#include "corr_alt_taps.h"
 
 namespace {
 
@@ -43,7 +44,6 @@ constexpr int NWIN = TQ + 4 + 1;
 constexpr int OFF_PLAN = OFF_WIN + NWIN * 16;                  // work items [count, then (first, G, X0, Y0, BW, BH) x 32]
 constexpr int LDS_BYTES = OFF_PLAN + (1 + 6 * TQ) * 4;
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU");
-constexpr int BIG = 1 << 24;          // tap indices are clamped to +-BIG for the window geometry (wild coordinates)
 
 struct AltArgs {
     const char* f1;           // [B*Q][1 KB] split pairs or fp32 fmap1
@@ -58,24 +58,6 @@ struct AltArgs {
     float scale;
 };
 
-// corr_lookup_dma.hip's taps_a for one axis: x = c 2^-l + off, g = 2 x / (n - 1) - 1 as the correctly rounded quotient (two
-// exact remainders), u = ((g + 1) / 2) (n - 1), corner floor(u), weight u - floor(u) - every step a separately rounded fp32
-// operation, so the corners and weights are bit-identical to the tiled lookup's (and to grid_sample's).
-__device__ __forceinline__ void tap(float c, float inv, float off, float nm1, float r2, int& i0, float& wgt) {
-    const float x = __fadd_rn(__fmul_rn(c, inv), off);
-    const float dh = 0.5f * nm1;
-    const float q0 = __fmul_rn(x, r2);
-    const float e0 = __builtin_fmaf(-q0, dh, x);
-    const float q1 = __builtin_fmaf(e0, r2, q0);
-    const float e1 = __builtin_fmaf(-q1, dh, x);
-    const float g = __fsub_rn(__builtin_fmaf(e1, r2, q1), 1.f);
-    const float u = __fmul_rn(__fmul_rn(__fadd_rn(g, 1.f), 0.5f), nm1);
-    const float f = floorf(u);
-    i0 = (int)f;
-    wgt = __fsub_rn(u, f);
-}
-
-__device__ __forceinline__ int clampi(int v) { return min(max(v, -BIG), BIG); }
 
 // One 32-position x 32-query block of D: rows = union positions p0 .. p0 + 31 (row-major over the BW-wide window at X0, Y0),
 // columns = queries first + (col % G) of the tile.

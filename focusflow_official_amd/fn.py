@@ -478,6 +478,43 @@ class LookupFn(torch.autograd.Function):
         return torch.zeros(1, device=dout.device), None, None
 
 
+class AltCorrBuildFn(torch.autograd.Function):
+    """(fmap1, fmap2) -> token for the on-the-fly correlation (corr_block.AlternateCorrBlock), built like CorrBuildFn: the
+    forward leaves the operand rows on `block` (block._ops); every AltLookupFn.backward only queues its (coords, dout), and
+    this node - which autograd runs after every lookup because of the token edge - issues the backward of all of them at
+    once (ops.corr_alt_lookup_bwd) and returns d fmap1, d fmap2."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, block):
+        block._ops = ops.corr_alt_prepare(f1, f2)
+        block.pending = []
+        ctx.block = block
+        ctx.save_for_backward(f1, f2)      # (the launch reads them through block._ops; saved, autograd checks them for in-place changes)
+        return torch.zeros(1, device=f1.device)
+
+    @staticmethod
+    def backward(ctx, dtoken):
+        _f1, _f2 = ctx.saved_tensors      # (raises if fmap1 / fmap2 were changed in place since the forward)
+        blk = ctx.block
+        pending, blk.pending = blk.pending or [], []
+        df1, df2 = ops.corr_alt_lookup_bwd(blk._ops, [c for c, _ in pending], [d for _, d in pending])
+        return df1, df2, None
+
+
+class AltLookupFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, token, block, coords):
+        ctx.block = block
+        ctx.save_for_backward(coords)
+        return ops.corr_alt_lookup(block._ops, coords)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (coords,) = ctx.saved_tensors
+        ctx.block.pending.append((coords, _dense(dout)))      # deferred to AltCorrBuildFn.backward (one launch per pass)
+        return torch.zeros(1, device=dout.device), None, None
+
+
 # ----------------------------------------------------------------------------
 # SA / CA fusion units (parallel_fusion.py:14-73)
 # ----------------------------------------------------------------------------

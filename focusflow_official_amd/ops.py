@@ -454,7 +454,7 @@ class AltOperands:
         return (C.c_void_p * 4)(*[lv.data_ptr() for lv in self.levels])
 
 
-TIME_ALT_LOOKUP, TIME_ALT_PREPARE = 4, 5                  # include/focusflow_hip.h: FF_TIME_*
+TIME_ALT_LOOKUP, TIME_ALT_PREPARE, TIME_ALT_LOOKUP_BWD = 4, 5, 6      # include/focusflow_hip.h: FF_TIME_*
 
 
 def corr_alt_prepare(fmap1: Tensor, fmap2: Tensor) -> AltOperands:
@@ -497,6 +497,49 @@ def corr_alt_lookup(ops: AltOperands, coords: Tensor, want_taps: bool = False, o
     _timed_call("lookup", "ff_corr_alt_lookup", _p(ops.f1), ops.ptrs(), int(ops.split), _p(coords), b, h, w, _p(out), _ld(out),
                 _p(taps), _stream())
     return (out, taps) if want_taps else out
+
+
+def corr_alt_lookup_bwd(ops: AltOperands, coords_list: List[Tensor], dout_list: List[Optional[Tensor]]):
+    """Backward of the on-the-fly lookups of one recorded pass (ff_corr_alt_lookup_bwd, one launch per 32 lookups + a fold):
+    coords_list[t] (B, H, W, 2) as the forward's lookup t saw them, dout_list[t] (B, H, W, 324) - or a (B, H, W, 324) view of
+    a wider NHWC buffer, or None (no gradient reached that lookup) -> (d fmap1, d fmap2), NHWC (B, H, W, 256).  Exact fp32
+    arithmetic in every precision: the split precisions get fp32 rows of levels 1-3 for the duration of the call."""
+    fmap1, fmap2 = ops._keep[0], ops._keep[1]
+    b, h, w = ops.b, ops.h0, ops.w0
+    pairs = [(c, d) for c, d in zip(coords_list, dout_list) if d is not None]
+    df1 = torch.empty((b, h, w, 256), dtype=torch.float32, device=fmap1.device)
+    if not pairs:
+        return df1.zero_(), torch.zeros_like(df1)
+    for c, d in pairs:
+        _require_gpu(c)
+        assert c.is_contiguous() and tuple(c.shape) == (b, h, w, 2) and tuple(d.shape) == (b, h, w, 324)
+    ld = {_ld(d) for _, d in pairs}
+    if len(ld) != 1:
+        pairs = [(c, d.contiguous()) for c, d in pairs]
+        ld = {324}
+    rows = [b * (h >> l) * (w >> l) for l in range(4)]
+    if ops.split:      # fp32 rows of levels 1-3 (ff_corr_alt_prepare with split == 0)
+        flat = torch.empty(sum(rows[1:]) * 256, dtype=torch.float32, device=fmap1.device)
+        lv32, o = [fmap2.view(rows[0], 256)], 0
+        for l in range(1, 4):
+            lv32.append(flat[o * 256:(o + rows[l]) * 256].view(rows[l], 256))
+            o += rows[l]
+        lv = (C.c_void_p * 4)(0, *[x.data_ptr() for x in lv32[1:]])
+        _hip.call("ff_corr_alt_prepare", _p(fmap1), _p(fmap2), b, h, w, 256, 0, C.c_void_p(0), lv, _stream())
+    else:
+        lv32 = ops.levels
+    df2 = torch.zeros((b, h, w, 256), dtype=torch.float32, device=fmap1.device)
+    scratch = torch.zeros(sum(rows[1:]) * 256, dtype=torch.float32, device=fmap1.device)
+    dl, o = [df2], 0
+    for l in range(1, 4):
+        dl.append(scratch[o * 256:(o + rows[l]) * 256])
+        o += rows[l]
+    n = len(pairs)
+    cl = (C.c_void_p * n)(*[c.data_ptr() for c, _ in pairs])
+    gl = (C.c_void_p * n)(*[d.data_ptr() for _, d in pairs])
+    _timed_call("corr_alt_lookup_bwd", "ff_corr_alt_lookup_bwd", _p(fmap1), (C.c_void_p * 4)(*[x.data_ptr() for x in lv32]), cl, gl, n,
+                ld.pop(), b, h, w, _p(df1), (C.c_void_p * 4)(*[x.data_ptr() for x in dl]), _stream())
+    return df1, df2
 
 
 def corr_volume(fmap1: Tensor, fmap2: Tensor) -> Tensor:

@@ -4,7 +4,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _hip, cce, fn, ops, train_loop
+from . import _hip, cce, corr_block, fn, ops, train_loop
 from .cce import BasicParallelFusionLayer, train_streams
 from .corr_block import AlternateCorrBlock, CorrBlock
 from .ops import ACT_RELU, ACT_TANH
@@ -32,7 +32,8 @@ class RAFT(nn.Module):
         self.dropout = dropout
         # ALT_CORR selects the on-the-fly correlation (corr_block.AlternateCorrBlock: memory linear in the image area instead
         # of B * Q^2 * 5.3 bytes) wherever the feature maps are not recorded - inference, frozen encoders; a pass that records
-        # them keeps the materialised pyramid, whose backward exists (_corr_block)
+        # them keeps the materialised pyramid (the faster lookup) while the batch's pyramid fits corr_block._MAX_PYRAMID_BYTES,
+        # and differentiates through the on-the-fly block beyond it (_corr_block)
         self.alternate_corr = alternate_corr
         self._alt_warned = False
         # storage type of the correlation pyramid: None = $FF_CORR_PYRAMID or "fp32"; "fp16" = BASELINE configs[4]
@@ -173,9 +174,16 @@ class RAFT(nn.Module):
                 return AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
             if not self._alt_warned:
                 import warnings
-                warnings.warn("alternate_corr=True: the feature maps are recorded (trained encoders), and the on-the-fly "
-                              "correlation has no backward - this model's recorded passes use the materialised all-pairs pyramid")
+                warnings.warn("alternate_corr=True: the feature maps are recorded (trained encoders) - a recorded batch whose "
+                              f"materialised all-pairs pyramid stays under {corr_block._MAX_PYRAMID_BYTES / 1e9:.2f} GB uses that "
+                              "pyramid (the faster lookup); larger batches use the on-the-fly correlation and its backward")
                 self._alt_warned = True
+            b, h, w, _ = fmap1.shape
+            if not corr_block.pyramid_fits(b, h, w, self.corr_pyramid_dtype):
+                # the fused update-loop node differentiates through the block itself: built outside the tape, as below
+                if fused_train:
+                    return AlternateCorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius)
+                return AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
         # the fused update-loop node takes the feature maps themselves - the pyramid is then built outside the tape
         if fused_train:
             return CorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
@@ -202,8 +210,11 @@ class RAFT(nn.Module):
                     return list(train_loop.UpdateLoopFn.apply(self.update_block, corr_fn, coords1, iters, loop_gate[0], net, *pre,
                                                               fmap1.contiguous(), fmap2.contiguous(), loop_gate[1]))
                 return list(train_loop.UpdateLoopFn.apply(self.update_block, corr_fn, coords1, iters, None, net, *pre, fmap1.contiguous(), fmap2.contiguous(), *lp))
-            if fn.recording(fmap1, fmap2):      # (not eligible after all: the per-operation tape needs the pyramid on the tape)
-                corr_fn = CorrBlock(fmap1, fmap2, radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
+            if fn.recording(fmap1, fmap2):      # (not eligible after all: the per-operation tape needs the block on the tape)
+                if isinstance(corr_fn, AlternateCorrBlock):
+                    corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
+                else:
+                    corr_fn = CorrBlock(fmap1, fmap2, radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
         flow4, flow_up, flow_predictions = self._loop(net, inp, corr_fn, coords1, gru_pre, iters, b, h8, w8, taped, test_mode)
         if test_mode:
             return ops.nhwc_to_nchw(flow4[..., :2]), flow_up

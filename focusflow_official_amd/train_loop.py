@@ -10,7 +10,8 @@ fixed sequence of libfocusflow_hip launches:
   * ONE weight-gradient launch per convolution for all T iterations: the stacks are ordinary batches of T * B images, so
     `ff_conv2d_wgrad` contracts over all of them at once (13 launches instead of 156);
   * the lookup gradients of all iterations scattered by one launch, then the two volume contractions (fn.CorrBuildFn's job
-    in the per-operation tape).
+    in the per-operation tape) - or, with the on-the-fly correlation (corr_block.AlternateCorrBlock), the backward of all
+    lookups in one launch that returns d fmap1, d fmap2 itself (ops.corr_alt_lookup_bwd, fn.AltCorrBuildFn's job).
 
 Parameter gradients leave this node once per parameter (DDP's reducer sees one gradient each).
 """
@@ -20,6 +21,7 @@ from typing import List, Optional
 import torch
 
 from . import _hip, fn, ops
+from .corr_block import AlternateCorrBlock
 from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH
 
 Tensor = torch.Tensor
@@ -121,9 +123,22 @@ def loop_params(ub) -> List[Optional[Tensor]]:
 
 def eligible(ub, corr_fn, net, gru_pre) -> bool:
     """The fused node covers the default configuration: split conv formats (their gradient kernels return the bias gradient
-    and scale by max|g|), the context share of the gates computed once, 128-channel state."""
+    and scale by max|g|), the context share of the gates computed once, 128-channel state; one materialised pyramid or the
+    on-the-fly correlation (built outside the tape: the node differentiates through it itself)."""
     return (ENABLED and gru_pre is not None and ops.w_format() in (_hip.W_F16X3, _hip.W_F16) and net.shape[3] == 128
-            and net.is_cuda and corr_fn.pyr is not None)
+            and net.is_cuda and (corr_fn.pyr is not None or (_on_the_fly(corr_fn) and corr_fn._token is None)))
+
+
+def _on_the_fly(corr_fn) -> bool:
+    return isinstance(corr_fn, AlternateCorrBlock)
+
+
+def _lookup(corr_fn, coords, out):
+    """One iteration's lookup into out (B, H, W, 324): the materialised pyramid's, or the on-the-fly correlation's."""
+    if _on_the_fly(corr_fn):
+        ops.corr_alt_lookup(corr_fn._ops, coords, out=out)
+    else:
+        ops.corr_lookup_tiled(corr_fn.pyr, coords, out=out)
 
 
 def _fwd(pc, xs, out, act=ACT_NONE, res=None, out_scale=1.0):
@@ -169,7 +184,7 @@ def _forward_fused(ub, corr_fn, coords1, T, net0, pre):
         lo, hi = t * b, (t + 1) * b
         S["coords"][t].copy_(coords1)
         corr = S["corr"][lo:hi]
-        ops.corr_lookup_tiled(corr_fn.pyr, S["coords"][t], out=corr[..., :324])
+        _lookup(corr_fn, S["coords"][t], corr[..., :324])
         c2f2, motion = S["c2f2"][lo:hi], S["motion"][lo:hi]
         # motion encoder (update.py:89-97): every tensor between its convolutions leaves as a split pair
         c1 = enc._c1p(corr, act=ACT_RELU, y_split=True, out=S["c1"][lo:hi])
@@ -244,7 +259,7 @@ class UpdateLoopFn(torch.autograd.Function):
             lo, hi = t * b, (t + 1) * b
             S["coords"][t].copy_(coords1)            # coords1 moves on in place: the backward scatter needs this iteration's
             corr = S["corr"][lo:hi]
-            ops.corr_lookup_tiled(corr_fn.pyr, S["coords"][t], out=corr[..., :324])
+            _lookup(corr_fn, S["coords"][t], corr[..., :324])
             c2f2, motion = S["c2f2"][lo:hi], S["motion"][lo:hi]
             # motion encoder (update.py:89-97)
             _fwd(enc._c1p, corr, S["c1"][lo:hi], ACT_RELU)
@@ -315,6 +330,7 @@ class UpdateLoopFn(torch.autograd.Function):
         d_c1 = torch.empty((b, h, w, 256), dtype=torch.float32, device=dev)
         d_f1 = torch.empty((b, h, w, 128), dtype=torch.float32, device=dev)
         dh_valid = False
+        reached = [False] * T                            # iterations some gradient reaches (the others' d corr is zero)
         st = ops._stream
         p = ops._p
         # ---- weight gradients: per convolution ONE buffer for all iterations, filled by a few launches over slabs of WCHUNK
@@ -372,6 +388,7 @@ class UpdateLoopFn(torch.autograd.Function):
                 dh_valid = True
             if not dh_valid:
                 continue                                     # nothing reaches this iteration (its G slices are zero)
+            reached[t] = True
             motion = S["motion"][lo:hi]
             later_zc = None
             for k in (1, 0):
@@ -414,7 +431,12 @@ class UpdateLoopFn(torch.autograd.Function):
             else:
                 grads.append(None)
         # lookup scatter + pooling chain + the two volume contractions (corr.py:29-60 backward)
-        if (need[NF + 5] or need[NF + 6]) and dh_valid:
+        if (need[NF + 5] or need[NF + 6]) and dh_valid and _on_the_fly(ctx.corr_fn):
+            # on-the-fly correlation: the backward of every reached lookup in one launch (+ the fold of the level planes)
+            df1, df2 = ops.corr_alt_lookup_bwd(ctx.corr_fn._ops, [S["coords"][t] for t in range(T)],
+                                               [G["dcorr"][t * b:(t + 1) * b][..., :324] if reached[t] else None for t in range(T)])
+            grads += [df1 if need[NF + 5] else None, df2 if need[NF + 6] else None]
+        elif (need[NF + 5] or need[NF + 6]) and dh_valid:
             pyr = ctx.corr_fn.pyr
             cl, dl = [S["coords"][t] for t in range(T)], [G["dcorr"][t * b:(t + 1) * b] for t in range(T)]
             d0 = None

@@ -72,7 +72,8 @@ int ff_abi_version(void);
 #define FF_TIME_PROBE 3         /* ff_probe_memory_kernel's kernel   */
 #define FF_TIME_ALT_LOOKUP 4    /* ff_corr_alt_lookup's kernel       */
 #define FF_TIME_ALT_PREPARE 5   /* ff_corr_alt_prepare's kernel      */
-#define FF_TIME_KINDS 5
+#define FF_TIME_ALT_LOOKUP_BWD 6 /* ff_corr_alt_lookup_bwd's main kernel */
+#define FF_TIME_KINDS 6
 int ff_launch_timing_begin(int which);
 int ff_launch_timing_end(int which, long long* launches, double* total_us, double* min_us, double* max_us);
 /* Measurement aid (probe.hip): a memory-only kernel with the lookup's launch shape (`blocks` one-wave blocks) and access
@@ -306,7 +307,7 @@ int ff_corr_pyramid_tiled_bwd(float* d0, float* d1, float* d2, const float* d3, 
 
 /* ------------------------------------------------------------------------
  * AlternateCorrBlock (FF_RAFT_Core/corr.py:63-91): CorrBlock.__call__'s numbers without the all-pairs pyramid (memory
- * linear in the image area; inference only - there is no backward).  fmap1 / fmap2: NHWC [B][h0][w0][C] fp32, C = 256.
+ * linear in the image area; ff_corr_alt_lookup_bwd is the backward of a pass's lookups).  fmap1 / fmap2: NHWC [B][h0][w0][C] fp32, C = 256.
  *   ff_corr_alt_prepare  once per pair of feature maps: pooled levels 1-3 of fmap2 (avg_pool2d(2, 2), floor semantics)
  *                        in the lookup's operand form.  split != 0 (the fp16-split precisions): f1_split [B*Q][1024 B] and
  *                        levels[0..3] [B*h_l*w_l][1024 B] receive split pairs in ff_pack_split_f16's row format.  split == 0
@@ -323,6 +324,19 @@ int ff_corr_alt_prepare(const float* fmap1, const float* fmap2, int B, int h0, i
 int ff_corr_alt_lookup(const void* f1, const void* const* levels /* HOST array of 4 device ptrs */, int split,
                        const float* coords /* [B*Q][2] x,y */, int B, int h0, int w0, float* out, int out_ld, int* taps,
                        void* stream);
+/* ff_corr_alt_lookup_bwd: the backward of T lookups of one recorded pass (every lookup whose output has a gradient).
+ *   levels    fp32 rows [B*h_l*w_l][C]: fmap2 and the levels 1-3 ff_corr_alt_prepare writes with split == 0 (the backward
+ *             runs in exact fp32 in every precision);  fmap1: [B*Q][C] fp32.
+ *   coords_list[t] [B*Q][2] x,y and dout_list[t] [B*Q][dout_ld] (channels 0..323, ff_corr_alt_lookup's order): HOST arrays
+ *             of T device pointers.  Any T: passes beyond the per-launch count are split into several launches.
+ *   d_fmap1   [B*Q][C], written (no zero fill needed).
+ *   d_levels  HOST array of 4 device ptrs, fp32 planes [B*h_l*w_l][C] that the caller ZEROES; the lookups' gradients are
+ *             added into them, then level 0 receives d fmap2 = d f2_0 + sum_{l>=1} unpool_l(d f2_l) / 4^l (avg_pool2d's floor
+ *             semantics); levels 1-3 are scratch afterwards.
+ * Coordinates outside the plane contribute nothing (CorrBlock's backward).  Nothing is allocated, nothing waits for the host. */
+int ff_corr_alt_lookup_bwd(const float* fmap1, const float* const* levels /* HOST array of 4 device ptrs */,
+                           const float* const* coords_list, const float* const* dout_list, int T, int dout_ld, int B, int h0,
+                           int w0, float* d_fmap1, float* const* d_levels /* HOST array of 4 device ptrs */, void* stream);
 
 /* ------------------------------------------------------------------------
  * Update-block glue (raft.py:205-231, update.py:45-60).

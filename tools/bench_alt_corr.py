@@ -6,6 +6,11 @@
     python tools/bench_alt_corr.py forward     whole-forward pairs/s, alternate_corr True vs False, same process, alternating
                                                (captured forwards, GraphedForward)
     python tools/bench_alt_corr.py highres     ms per pair and max_memory_allocated at 1088x1920 and 2160x3840, 12 iterations
+    python tools/bench_alt_corr.py --train     recorded passes (trained encoders): the training step (forward + backward,
+                                               12 iterations, 8x368x496) on the on-the-fly route - forced by lowering
+                                               corr_block._MAX_PYRAMID_BYTES - against the materialised one, alternating in
+                                               one process; the backward kernel's time per pass (ff_corr_alt_lookup_bwd); one
+                                               recorded 1088x1920 step under FF_CONV_PRECISION=fp32, time and max_memory_allocated
 
 Roofline: a query needs 4 x 100 dot products of 256 channels = 102 400 MACs.  The split precisions issue them as three f16
 MFMA products each (2.5 PFLOP/s dense f16), the exact-fp32 one as 32x32x2 fp32 MFMAs (157 TFLOP/s).  Minimal bytes of a
@@ -113,6 +118,69 @@ def forward(rounds, reps):
         torch.cuda.empty_cache()
 
 
+def _train_step(m, inp, iters, w):
+    for p in m.parameters():
+        p.grad = None
+    preds = m(*inp, raft_iters=iters)
+    sum((p * x).sum() for p, x in zip(preds, w)).backward()
+
+
+def train(rounds, reps):
+    import warnings
+    from focusflow_official_amd import corr_block
+    warnings.simplefilter("ignore")
+    default = corr_block._MAX_PYRAMID_BYTES
+    b, h, w, iters = 8, 368, 496, 12
+    m = _model(True).train()
+    inp = _inputs(b, h, w)
+    g = torch.Generator().manual_seed(5)
+    wts = [(torch.randn(b, 2, h, w, generator=g) * 1e-3).to(DEV) for _ in range(iters)]
+    per = {"materialised": [], "on-the-fly": []}
+    for _ in range(rounds):
+        for route in per:
+            corr_block._MAX_PYRAMID_BYTES = default if route == "materialised" else 1
+            _train_step(m, inp, iters, wts)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                _train_step(m, inp, iters, wts)
+            torch.cuda.synchronize()
+            per[route].append((time.perf_counter() - t0) * 1e3 / reps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+    print(f"  {b}x{h}x{w} it{iters} recorded step (fwd + bwd, fused update-loop node): materialised {med['materialised']:.2f} ms, "
+          f"on-the-fly {med['on-the-fly']:.2f} ms, ratio {med['on-the-fly'] / med['materialised']:.3f}  (median of {rounds} "
+          f"alternating rounds of {reps} steps; all: {[round(x, 2) for x in per['materialised']]} / {[round(x, 2) for x in per['on-the-fly']]})")
+    corr_block._MAX_PYRAMID_BYTES = 1
+    ops.launch_timing_begin(ops.TIME_ALT_LOOKUP_BWD)
+    for _ in range(reps):
+        _train_step(m, inp, iters, wts)
+    n, tot, lo, hi = ops.launch_timing_end(ops.TIME_ALT_LOOKUP_BWD)
+    print(f"  {b}x{h}x{w} it{iters} ff_corr_alt_lookup_bwd main kernel: {tot / max(n, 1):.1f} us per pass (min {lo:.1f}, max {hi:.1f}, "
+          f"{n} launches)")
+    corr_block._MAX_PYRAMID_BYTES = default
+    del m, inp, wts
+    torch.cuda.empty_cache()
+    # one recorded 1088x1920 pair in fp32 (its materialised pyramid, 5.7 GB, is beyond the lookup's resource: the on-the-fly
+    # route is selected by the size itself)
+    ops.set_conv_precision("fp32")
+    m = _model(True).train()
+    inp = _inputs(1, 1088, 1920)
+    wts = [(torch.randn(1, 2, 1088, 1920, generator=g) * 1e-3).to(DEV) for _ in range(iters)]
+    _train_step(m, inp, iters, wts)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    nrep = max(1, reps // 4)
+    for _ in range(nrep):
+        _train_step(m, inp, iters, wts)
+    torch.cuda.synchronize()
+    finite = all(bool(torch.isfinite(p.grad).all()) for p in m.parameters() if p.grad is not None)
+    print(f"  1x1088x1920 it{iters} recorded step FF_CONV_PRECISION=fp32 alternate_corr=True: "
+          f"{(time.perf_counter() - t0) * 1e3 / nrep:.1f} ms, max_memory_allocated {torch.cuda.max_memory_allocated() / 1e9:.2f} GB, "
+          f"gradients finite: {finite}")
+    ops.set_conv_precision("f16x3")
+
+
 def highres(reps, precision):
     ops.set_conv_precision(precision)
     m = _model(True)
@@ -139,10 +207,16 @@ def highres(reps, precision):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("kernels", "forward", "highres"))
+    ap.add_argument("what", nargs="?", choices=("kernels", "forward", "highres", "train"))
+    ap.add_argument("--train", action="store_true", help="the recorded-pass leg (= what 'train')")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--precision", default="f16x3", help="FF_CONV_PRECISION of the highres leg")
     a = ap.parse_args()
+    if a.train:
+        a.what = "train"
+    if a.what is None:
+        ap.error("name a leg (kernels, forward, highres) or pass --train")
     print(f"{torch.cuda.get_device_name(0)}  bench_alt_corr {a.what}")
-    {"kernels": lambda: kernels(a.reps), "forward": lambda: forward(a.rounds, a.reps), "highres": lambda: highres(max(1, a.reps // 10), a.precision)}[a.what]()
+    {"kernels": lambda: kernels(a.reps), "forward": lambda: forward(a.rounds, a.reps), "highres": lambda: highres(max(1, a.reps // 10), a.precision),
+     "train": lambda: train(a.rounds, max(2, a.reps // 2))}[a.what]()
