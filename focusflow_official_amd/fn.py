@@ -183,7 +183,6 @@ def unpack_group(pc, dw: Tensor, db: Tensor) -> List[Optional[Tensor]]:
 
 _scope: Optional[GraphScope] = None
 _UNPACK_GROUP = True     # one gradient-unpacking launch per packed convolution (tests switch it off to compare)
-_LOOKUP_BWD_ALL = True   # one lookup-backward launch per pass instead of one per iteration
 _ZERO_ARENA = True       # one zero fill per pass for the backward's accumulation buffers
 _AMAX_HINT = True        # the norm backward measures max|dx| for the conv it feeds
 _RES_GRAD_FUSED = os.environ.get("FF_TRAIN_RES_GRAD", "1") != "0"      # A/B switch: a residual block's skip gradient added inside its first convolution's input-gradient launch
@@ -406,47 +405,23 @@ class UpsampleFn(torch.autograd.Function):
         return None, dflow, dmask
 
 
-# ---- CorrBlock -------------------------------------------------------------
+# ---- correlation blocks --------------------------------------------------------
 class CorrBuildFn(torch.autograd.Function):
-    """(fmap1, fmap2) -> token.  The tiled pyramid lives on `block` (block.pyr); lookups accumulate their gradients
-    into block.grad_pyr (tiled fp32 planes - no per-iteration volume-sized autograd buffers), and this node - which
-    autograd runs after every LookupFn because of the token edge - folds them down the pooling chain to d(volume) and
-    contracts that with the feature maps (BmmBackward of corr.py:58).  fp16 pyramid storage is a straight-through
-    rounding for the gradient, as a cast under autocast would be."""
+    """(fmap1, fmap2) -> token: builds `block` (corr_block.CorrBlock / AlternateCorrBlock) from recorded feature maps.  Every
+    LookupFn hands its gradient to block.grad_add; this node - which autograd runs after every LookupFn because of the token
+    edge - takes d fmap1, d fmap2 from block.grad_finish."""
 
     @staticmethod
-    def forward(ctx, f1, f2, block, half):
-        block.pyr = ops.corr_build(f1, f2, half)
-        block.grad_pyr = None
+    def forward(ctx, f1, f2, block):
+        block.build(f1, f2)
         ctx.block = block
         ctx.save_for_backward(f1, f2)
         return torch.zeros(1, device=f1.device)
 
     @staticmethod
     def backward(ctx, dtoken):
-        f1, f2 = ctx.saved_tensors
-        blk = ctx.block
-        b, h, w, _ = f1.shape
-        pending, blk.pending = getattr(blk, "pending", None), None
-        if pending:
-            # every lookup of the pass in one launch (+ the pooling chain): LookupFn.backward only queues where that launch
-            # is going to accept the pass (plane sizes and count checked up front), so a refusal here is a library change
-            d0 = ops.corr_lookup_tiled_bwd_all([c for c, _ in pending], [d for _, d in pending], blk.pyr.h0, blk.pyr.w0)
-            if d0 is None:
-                if blk.grad_pyr is None:
-                    blk.grad_pyr = ops.TiledPyramid.empty(blk.pyr.levels[0].shape[0], blk.pyr.h0, blk.pyr.w0, False, f1.device, zero=True)
-                for c, d in pending:
-                    ops.corr_lookup_tiled_bwd(blk.grad_pyr, c, d)
-            else:
-                df1, df2 = ops.corr_volume_bwd(d0.view(b, h * w, -1), f1, f2, tiled=True)
-                return df1, df2, None, None
-        gp = blk.grad_pyr
-        if gp is None:
-            return torch.zeros_like(f1), torch.zeros_like(f2), None, None
-        ops.corr_pyramid_tiled_bwd(gp)
-        blk.grad_pyr = None
-        df1, df2 = ops.corr_volume_bwd(gp.levels[0].view(b, h * w, -1), f1, f2, tiled=True)
-        return df1, df2, None, None
+        f1, f2 = ctx.saved_tensors      # (raises if fmap1 / fmap2 were changed in place since the forward)
+        return (*ctx.block.grad_finish(f1, f2), None)
 
 
 class LookupFn(torch.autograd.Function):
@@ -454,64 +429,12 @@ class LookupFn(torch.autograd.Function):
     def forward(ctx, token, block, coords):
         ctx.block = block
         ctx.save_for_backward(coords)
-        return ops.corr_lookup_tiled(block.pyr, coords)
+        return block.lookup(coords)
 
     @staticmethod
     def backward(ctx, dout):
         (coords,) = ctx.saved_tensors
-        blk = ctx.block
-        # deferred: the gradient of the pyramid is a sum over the lookups and nothing reads it before CorrBuildFn.backward,
-        # which scatters all of them in one launch (ops.corr_lookup_tiled_bwd_all) - where that launch exists for the
-        # pass: a query's four planes must fit its LDS and it takes at most LOOKUP_BWD_ALL_MAX lookups.  Otherwise the
-        # gradient is scattered right away and nothing is retained (large crops would keep every dout alive on top of
-        # the zeroed gradient pyramid).
-        pend = getattr(blk, "pending", None) or []
-        if _LOOKUP_BWD_ALL and blk.grad_pyr is None and len(pend) < ops.LOOKUP_BWD_ALL_MAX and ops.lookup_bwd_all_fits(blk.pyr.h0, blk.pyr.w0):
-            pend.append((coords, _dense(dout)))
-            blk.pending = pend
-        else:
-            if blk.grad_pyr is None:
-                blk.grad_pyr = ops.TiledPyramid.empty(blk.pyr.levels[0].shape[0], blk.pyr.h0, blk.pyr.w0, False, dout.device, zero=True)
-            blk.pending = None
-            for c, d in pend + [(coords, _dense(dout))]:       # (the queue is only non-empty when the pass has more lookups than one launch takes)
-                ops.corr_lookup_tiled_bwd(blk.grad_pyr, c, d)
-        return torch.zeros(1, device=dout.device), None, None
-
-
-class AltCorrBuildFn(torch.autograd.Function):
-    """(fmap1, fmap2) -> token for the on-the-fly correlation (corr_block.AlternateCorrBlock), built like CorrBuildFn: the
-    forward leaves the operand rows on `block` (block._ops); every AltLookupFn.backward only queues its (coords, dout), and
-    this node - which autograd runs after every lookup because of the token edge - issues the backward of all of them at
-    once (ops.corr_alt_lookup_bwd) and returns d fmap1, d fmap2."""
-
-    @staticmethod
-    def forward(ctx, f1, f2, block):
-        block._ops = ops.corr_alt_prepare(f1, f2)
-        block.pending = []
-        ctx.block = block
-        ctx.save_for_backward(f1, f2)      # (the launch reads them through block._ops; saved, autograd checks them for in-place changes)
-        return torch.zeros(1, device=f1.device)
-
-    @staticmethod
-    def backward(ctx, dtoken):
-        _f1, _f2 = ctx.saved_tensors      # (raises if fmap1 / fmap2 were changed in place since the forward)
-        blk = ctx.block
-        pending, blk.pending = blk.pending or [], []
-        df1, df2 = ops.corr_alt_lookup_bwd(blk._ops, [c for c, _ in pending], [d for _, d in pending])
-        return df1, df2, None
-
-
-class AltLookupFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, token, block, coords):
-        ctx.block = block
-        ctx.save_for_backward(coords)
-        return ops.corr_alt_lookup(block._ops, coords)
-
-    @staticmethod
-    def backward(ctx, dout):
-        (coords,) = ctx.saved_tensors
-        ctx.block.pending.append((coords, _dense(dout)))      # deferred to AltCorrBuildFn.backward (one launch per pass)
+        ctx.block.grad_add(coords, _dense(dout))
         return torch.zeros(1, device=dout.device), None, None
 
 

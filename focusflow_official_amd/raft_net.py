@@ -169,9 +169,10 @@ class RAFT(nn.Module):
         return None
 
     def _corr_block(self, fmap1, fmap2, fused_train):
-        if self.alternate_corr:
-            if not fn.recording(fmap1, fmap2):
-                return AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
+        """The correlation block of this pass.  fused_train: the fused update-loop node takes the feature maps themselves and
+        differentiates through the block itself - the block is then built outside the tape."""
+        on_the_fly = self.alternate_corr
+        if on_the_fly and fn.recording(fmap1, fmap2):
             if not self._alt_warned:
                 import warnings
                 warnings.warn("alternate_corr=True: the feature maps are recorded (trained encoders) - a recorded batch whose "
@@ -179,14 +180,11 @@ class RAFT(nn.Module):
                               "pyramid (the faster lookup); larger batches use the on-the-fly correlation and its backward")
                 self._alt_warned = True
             b, h, w, _ = fmap1.shape
-            if not corr_block.pyramid_fits(b, h, w, self.corr_pyramid_dtype):
-                # the fused update-loop node differentiates through the block itself: built outside the tape, as below
-                if fused_train:
-                    return AlternateCorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius)
-                return AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
-        # the fused update-loop node takes the feature maps themselves - the pyramid is then built outside the tape
+            on_the_fly = not corr_block.pyramid_fits(b, h, w, self.corr_pyramid_dtype)
         if fused_train:
-            return CorrBlock(fmap1.detach(), fmap2.detach(), radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
+            fmap1, fmap2 = fmap1.detach(), fmap2.detach()
+        if on_the_fly:
+            return AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
         return CorrBlock(fmap1, fmap2, radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
 
     def _update_loop(self, net, inp, fmap1, fmap2, coords1, iters, loop_gate=None, corr_fn=None, test_mode=False):
@@ -211,10 +209,7 @@ class RAFT(nn.Module):
                                                               fmap1.contiguous(), fmap2.contiguous(), loop_gate[1]))
                 return list(train_loop.UpdateLoopFn.apply(self.update_block, corr_fn, coords1, iters, None, net, *pre, fmap1.contiguous(), fmap2.contiguous(), *lp))
             if fn.recording(fmap1, fmap2):      # (not eligible after all: the per-operation tape needs the block on the tape)
-                if isinstance(corr_fn, AlternateCorrBlock):
-                    corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.corr_radius)
-                else:
-                    corr_fn = CorrBlock(fmap1, fmap2, radius=self.corr_radius, pyramid_dtype=self.corr_pyramid_dtype)
+                corr_fn = self._corr_block(fmap1, fmap2, False)
         flow4, flow_up, flow_predictions = self._loop(net, inp, corr_fn, coords1, gru_pre, iters, b, h8, w8, taped, test_mode)
         if test_mode:
             return ops.nhwc_to_nchw(flow4[..., :2]), flow_up

@@ -9,9 +9,8 @@ fixed sequence of libfocusflow_hip launches:
     gradient sum between them in three element-wise kernels per iteration (csrc/train_ops.hip) - no accumulation launch;
   * ONE weight-gradient launch per convolution for all T iterations: the stacks are ordinary batches of T * B images, so
     `ff_conv2d_wgrad` contracts over all of them at once (13 launches instead of 156);
-  * the lookup gradients of all iterations scattered by one launch, then the two volume contractions (fn.CorrBuildFn's job
-    in the per-operation tape) - or, with the on-the-fly correlation (corr_block.AlternateCorrBlock), the backward of all
-    lookups in one launch that returns d fmap1, d fmap2 itself (ops.corr_alt_lookup_bwd, fn.AltCorrBuildFn's job).
+  * the lookup gradients of all iterations handed to the correlation block (grad_add), which returns d fmap1, d fmap2
+    (grad_finish) - the backward the per-operation tape takes through fn.CorrBuildFn.
 
 Parameter gradients leave this node once per parameter (DDP's reducer sees one gradient each).
 """
@@ -21,7 +20,6 @@ from typing import List, Optional
 import torch
 
 from . import _hip, fn, ops
-from .corr_block import AlternateCorrBlock
 from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH
 
 Tensor = torch.Tensor
@@ -123,22 +121,10 @@ def loop_params(ub) -> List[Optional[Tensor]]:
 
 def eligible(ub, corr_fn, net, gru_pre) -> bool:
     """The fused node covers the default configuration: split conv formats (their gradient kernels return the bias gradient
-    and scale by max|g|), the context share of the gates computed once, 128-channel state; one materialised pyramid or the
-    on-the-fly correlation (built outside the tape: the node differentiates through it itself)."""
+    and scale by max|g|), the context share of the gates computed once, 128-channel state; a correlation block the node can
+    differentiate through itself (corr_fn.fusable)."""
     return (ENABLED and gru_pre is not None and ops.w_format() in (_hip.W_F16X3, _hip.W_F16) and net.shape[3] == 128
-            and net.is_cuda and (corr_fn.pyr is not None or (_on_the_fly(corr_fn) and corr_fn._token is None)))
-
-
-def _on_the_fly(corr_fn) -> bool:
-    return isinstance(corr_fn, AlternateCorrBlock)
-
-
-def _lookup(corr_fn, coords, out):
-    """One iteration's lookup into out (B, H, W, 324): the materialised pyramid's, or the on-the-fly correlation's."""
-    if _on_the_fly(corr_fn):
-        ops.corr_alt_lookup(corr_fn._ops, coords, out=out)
-    else:
-        ops.corr_lookup_tiled(corr_fn.pyr, coords, out=out)
+            and net.is_cuda and corr_fn.fusable)
 
 
 def _fwd(pc, xs, out, act=ACT_NONE, res=None, out_scale=1.0):
@@ -184,7 +170,7 @@ def _forward_fused(ub, corr_fn, coords1, T, net0, pre):
         lo, hi = t * b, (t + 1) * b
         S["coords"][t].copy_(coords1)
         corr = S["corr"][lo:hi]
-        _lookup(corr_fn, S["coords"][t], corr[..., :324])
+        corr_fn.lookup(S["coords"][t], out=corr[..., :324])
         c2f2, motion = S["c2f2"][lo:hi], S["motion"][lo:hi]
         # motion encoder (update.py:89-97): every tensor between its convolutions leaves as a split pair
         c1 = enc._c1p(corr, act=ACT_RELU, y_split=True, out=S["c1"][lo:hi])
@@ -259,7 +245,7 @@ class UpdateLoopFn(torch.autograd.Function):
             lo, hi = t * b, (t + 1) * b
             S["coords"][t].copy_(coords1)            # coords1 moves on in place: the backward scatter needs this iteration's
             corr = S["corr"][lo:hi]
-            _lookup(corr_fn, S["coords"][t], corr[..., :324])
+            corr_fn.lookup(S["coords"][t], out=corr[..., :324])
             c2f2, motion = S["c2f2"][lo:hi], S["motion"][lo:hi]
             # motion encoder (update.py:89-97)
             _fwd(enc._c1p, corr, S["c1"][lo:hi], ACT_RELU)
@@ -430,25 +416,12 @@ class UpdateLoopFn(torch.autograd.Function):
                 grads.append(dst)
             else:
                 grads.append(None)
-        # lookup scatter + pooling chain + the two volume contractions (corr.py:29-60 backward)
-        if (need[NF + 5] or need[NF + 6]) and dh_valid and _on_the_fly(ctx.corr_fn):
-            # on-the-fly correlation: the backward of every reached lookup in one launch (+ the fold of the level planes)
-            df1, df2 = ops.corr_alt_lookup_bwd(ctx.corr_fn._ops, [S["coords"][t] for t in range(T)],
-                                               [G["dcorr"][t * b:(t + 1) * b][..., :324] if reached[t] else None for t in range(T)])
-            grads += [df1 if need[NF + 5] else None, df2 if need[NF + 6] else None]
-        elif (need[NF + 5] or need[NF + 6]) and dh_valid:
-            pyr = ctx.corr_fn.pyr
-            cl, dl = [S["coords"][t] for t in range(T)], [G["dcorr"][t * b:(t + 1) * b] for t in range(T)]
-            d0 = None
-            if T <= ops.LOOKUP_BWD_ALL_MAX and ops.lookup_bwd_all_fits(pyr.h0, pyr.w0) and fn._LOOKUP_BWD_ALL:
-                d0 = ops.corr_lookup_tiled_bwd_all(cl, dl, pyr.h0, pyr.w0)
-            if d0 is None:
-                gp = ops.TiledPyramid.empty(pyr.levels[0].shape[0], pyr.h0, pyr.w0, False, dev, zero=True)
-                for c, d in zip(cl, dl):
-                    ops.corr_lookup_tiled_bwd(gp, c, d)
-                ops.corr_pyramid_tiled_bwd(gp)
-                d0 = gp.levels[0]
-            df1, df2 = ops.corr_volume_bwd(d0.view(b, h * w, -1), fmap1, fmap2, tiled=True)
+        # the lookups' backward (corr.py:29-60 backward): the correlation block's, as on the per-operation tape
+        if (need[NF + 5] or need[NF + 6]) and dh_valid:
+            for t in range(T):
+                if reached[t]:
+                    ctx.corr_fn.grad_add(S["coords"][t], G["dcorr"][t * b:(t + 1) * b][..., :324])
+            df1, df2 = ctx.corr_fn.grad_finish(fmap1, fmap2)
             grads += [df1 if need[NF + 5] else None, df2 if need[NF + 6] else None]
         else:
             grads += [None, None]

@@ -1,5 +1,5 @@
-"""The backward of the on-the-fly correlation (csrc/corr_alt_bwd.hip, ops.corr_alt_lookup_bwd) in recorded passes: the token
-pair fn.AltCorrBuildFn / AltLookupFn behind corr_block.AlternateCorrBlock, the fused update-loop node on that block
+"""The backward of the on-the-fly correlation (csrc/corr_alt_bwd.hip, ops.corr_alt_lookup_bwd) in recorded passes:
+corr_block.AlternateCorrBlock behind the token pair fn.CorrBuildFn / LookupFn, the fused update-loop node on that block
 (train_loop.UpdateLoopFn) and RAFT's route for alternate_corr=True when a recorded batch's pyramid passes
 corr_block._MAX_PYRAMID_BYTES.
 

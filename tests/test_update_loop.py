@@ -233,10 +233,10 @@ CASES = {
 def test_update_loop_against_fp64_and_the_tape(raft, det_sd, case, monkeypatch):
     """The fused node under one switch setting against fp64, and against the per-operation tape on the same inputs; the
     tape against fp64 too."""
-    from focusflow_official_amd import fn, train_loop
+    from focusflow_official_amd import corr_block, train_loop
     switches, spec, grad_fmaps, frozen = CASES[case]
     for k, v in switches.items():
-        monkeypatch.setattr(fn if k == "_LOOKUP_BWD_ALL" else train_loop, k, v)
+        monkeypatch.setattr(corr_block if k == "_LOOKUP_BWD_ALL" else train_loop, k, v)
     ins = _inputs(**spec)
     key = tuple(sorted((k, str(v)) for k, v in spec.items()))
     r64, r32 = _oracle(det_sd, key, ins, torch.float64), _oracle(det_sd, key, ins, torch.float32)
