@@ -524,48 +524,29 @@ class FusionUnit(nn.Module):
         return mask_out, img_out
 
 
-class BasicParallelFusionLayer(nn.Module):
-    """CCE = frame branch (FFE) + condition branch (CFE) + 5 fusion units.
+class _ResidualEncoder(nn.Module):
+    """The frame branch's layers and how they run (extractor.py:118-192): 7x7 stride-2 stem + norm, three residual
+    stages (64 / 96 / 128 channels), 1x1 output convolution.  One body of code for plain RAFT's BasicEncoder and the
+    CCE's frame branch (BasicParallelFusionLayer); subclasses set `norm_fn`, call _frame_layers() and own `_stem` /
+    `_out` (PackedConv of conv1 / conv2)."""
 
-    Same constructor and attribute names as parallel_fusion.py:153-209; call
-    with NHWC4 tensors from ops.prep_input, returns NHWC (B, H/8, W/8, output_dim).
-    """
-
-    def __init__(self, img_channel=3, mask_channel=3, output_dim=128, norm_fn="batch", dropout=0, cfg=None):
-        super().__init__()
-        self.norm_fn = norm_fn
-        self.fusion_type = cfg.MODEL.FUSION_TYPE
-        if dropout and dropout > 0:
-            raise NotImplementedError("dropout > 0 is not used by any reference config and is not built")
-        self.norm1 = _make_norm(norm_fn, 64)
-        self.conv1 = nn.Conv2d(img_channel, 64, 7, stride=2, padding=3)
+    def _frame_layers(self, in_channel, output_dim):
+        """norm1, conv1, layer1-3, conv2 in the reference's registration order (norm1 before conv1)."""
+        self.norm1 = _make_norm(self.norm_fn, 64)
+        self.conv1 = nn.Conv2d(in_channel, 64, 7, stride=2, padding=3)
         self.layer1 = self._stage(64, 64, 1)
         self.layer2 = self._stage(64, 96, 2)
         self.layer3 = self._stage(96, 128, 2)
         self.conv2 = nn.Conv2d(128, output_dim, 1)
-        self.mask_norm1 = _make_norm(norm_fn, 64)
-        self.mask_conv1 = nn.Conv2d(mask_channel, 64, 7, stride=2, padding=3)
-        self.fusion1 = FusionUnit(64, self.fusion_type, True)
-        self.fusion2 = FusionUnit(64, self.fusion_type, True)
-        self.fusion3 = FusionUnit(96, self.fusion_type, True)
-        self.fusion4 = FusionUnit(128, self.fusion_type, True)
-        self.fusion5 = FusionUnit(output_dim, self.fusion_type, False)
-        self.mask_layer1 = self._stage(64, 64, 1)
-        self.mask_layer2 = self._stage(64, 96, 2)
-        self.mask_layer3 = self._stage(96, 128, 2)
-        self.mask_conv2 = nn.Conv2d(128, output_dim, 1)
-        self.dropout = None
-        # parallel_fusion.py:198-205 initialisation
+
+    def _init_weights(self):
+        # extractor.py:150-157, parallel_fusion.py:198-205
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
-        self._stem = PackedConv([self.conv1], 4)
-        self._mstem = PackedConv([self.mask_conv1], 4)
-        self._out = PackedConv([self.conv2])
-        self._mout = PackedConv([self.mask_conv2])
 
     def _stage(self, cin, cout, stride):
         return nn.Sequential(ResidualBlock(cin, cout, self.norm_fn, stride), ResidualBlock(cout, cout, self.norm_fn, 1))
@@ -645,6 +626,72 @@ class BasicParallelFusionLayer(nn.Module):
             return self._block(stage[1], self._block(stage[0], x), True)
         return self._block(stage[1], self._block(stage[0], x))
 
+    def _run_stem(self, x, lazy=False):
+        return self._conv_norm(x, self._stem, self.norm1, ACT_RELU, lazy=lazy)
+
+    def _run_out(self, x):
+        return fn.conv(self._out, x)
+
+
+class BasicEncoder(_ResidualEncoder):
+    """Plain RAFT's feature / context encoder (extractor.py:118-192): the CCE's frame branch without the mask branch
+    and the fusion units.  Same constructor and parameter names as the reference; call with an NHWC4 tensor from
+    ops.prep_input, returns NHWC (B, H/8, W/8, output_dim).  `mask` is accepted and ignored, so that RAFT calls both
+    encoder types alike."""
+
+    def __init__(self, in_channel=3, output_dim=128, norm_fn="batch", dropout=0.0):
+        super().__init__()
+        self.norm_fn = norm_fn
+        if dropout and dropout > 0:
+            raise NotImplementedError("dropout > 0 is not used by any reference config and is not built")
+        if in_channel > 4:
+            raise NotImplementedError(f"in_channel={in_channel}: the stem reads the NHWC4 images of ops.prep_input (at most 4 channels)")
+        self._frame_layers(in_channel, output_dim)
+        self.dropout = None
+        self._init_weights()
+        self._stem = PackedConv([self.conv1], 4)
+        self._out = PackedConv([self.conv2])
+
+    def forward(self, x, mask=None):
+        x = self._run_stem(x)
+        x = self._run_stage(self.layer1, x)
+        x = self._run_stage(self.layer2, x)
+        x = self._run_stage(self.layer3, x)
+        return self._run_out(x)
+
+
+class BasicParallelFusionLayer(_ResidualEncoder):
+    """CCE = frame branch (FFE) + condition branch (CFE) + 5 fusion units.
+
+    Same constructor and attribute names as parallel_fusion.py:153-209; call
+    with NHWC4 tensors from ops.prep_input, returns NHWC (B, H/8, W/8, output_dim).
+    """
+
+    def __init__(self, img_channel=3, mask_channel=3, output_dim=128, norm_fn="batch", dropout=0, cfg=None):
+        super().__init__()
+        self.norm_fn = norm_fn
+        self.fusion_type = cfg.MODEL.FUSION_TYPE
+        if dropout and dropout > 0:
+            raise NotImplementedError("dropout > 0 is not used by any reference config and is not built")
+        self._frame_layers(img_channel, output_dim)
+        self.mask_norm1 = _make_norm(norm_fn, 64)
+        self.mask_conv1 = nn.Conv2d(mask_channel, 64, 7, stride=2, padding=3)
+        self.fusion1 = FusionUnit(64, self.fusion_type, True)
+        self.fusion2 = FusionUnit(64, self.fusion_type, True)
+        self.fusion3 = FusionUnit(96, self.fusion_type, True)
+        self.fusion4 = FusionUnit(128, self.fusion_type, True)
+        self.fusion5 = FusionUnit(output_dim, self.fusion_type, False)
+        self.mask_layer1 = self._stage(64, 64, 1)
+        self.mask_layer2 = self._stage(64, 96, 2)
+        self.mask_layer3 = self._stage(96, 128, 2)
+        self.mask_conv2 = nn.Conv2d(128, output_dim, 1)
+        self.dropout = None
+        self._init_weights()
+        self._stem = PackedConv([self.conv1], 4)
+        self._mstem = PackedConv([self.mask_conv1], 4)
+        self._out = PackedConv([self.conv2])
+        self._mout = PackedConv([self.mask_conv2])
+
     def _branches(self, fm, fx, m, x):
         """(fm(m), fx(x)): the mask branch and the image branch between two fusion units are independent.  Inference runs
         the mask branch on a side stream (forked and joined with events: capturable): one branch's memory-bound norm passes
@@ -683,7 +730,7 @@ class BasicParallelFusionLayer(nn.Module):
         lz2 = self._lazy_for(self.fusion2, 64, hh // 2, ww // 2)
         lz3 = self._lazy_for(self.fusion3, 96, hh // 4, ww // 4)
         m, x = self._branches(lambda t: self._conv_norm(t, self._mstem, self.mask_norm1, ACT_RELU, lazy=lz1),
-                              lambda t: self._conv_norm(t, self._stem, self.norm1, ACT_RELU, lazy=lz1), mask, x)
+                              lambda t: self._run_stem(t, lz1), mask, x)
         m, x = self.fusion1.run(m, x)
         m, x = self._branches(lambda t: self._run_stage(self.mask_layer1, t, lz2), lambda t: self._run_stage(self.layer1, t, lz2), m, x)
         m, x = self.fusion2.run(m, x)
@@ -691,7 +738,7 @@ class BasicParallelFusionLayer(nn.Module):
         m, x = self.fusion3.run(m, x)
         m, x = self._branches(lambda t: self._run_stage(self.mask_layer3, t), lambda t: self._run_stage(self.layer3, t), m, x)
         m, x = self.fusion4.run(m, x)
-        m, x = fn.conv(self._mout, m), fn.conv(self._out, x)
+        m, x = fn.conv(self._mout, m), self._run_out(x)
         m, x = self.fusion5.run(m, x)
         return x
 

@@ -19,7 +19,7 @@ class GraphedForward:
         if model.training:
             raise ValueError("capture the eval-mode forward (training mutates BatchNorm buffers and the tape)")
         self.model, self.iters = model, raft_iters
-        self.static_in = [t.clone() for t in example_inputs]
+        self.static_in = [t.clone() if t is not None else None for t in example_inputs]    # (plain RAFT: masks may be None)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
@@ -41,7 +41,7 @@ class GraphedForward:
 
     def __call__(self, *inputs):
         for dst, src in zip(self.static_in, inputs):
-            if dst.data_ptr() != src.data_ptr():
+            if dst is not None and dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         ops.guard_check()                   # (raises if an earlier replay left the split formats' range)
         self.graph.replay()

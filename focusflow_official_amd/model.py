@@ -46,19 +46,31 @@ class FF_RAFT_FUSION(nn.Module):
                  cfg=None):
         super().__init__()
         _hip.load()  # fail now, loudly, if the HIP library has not been built
-        if use_fusion != "parallel":
+        if use_fusion not in (None, "parallel"):
             raise NotImplementedError(
-                f"use_fusion={use_fusion!r}: only the 'parallel' (CCE) front-end is on the HIP path; "
-                "'attention'/'conv' are selected by no shipped config (SURVEY §2.1 #8)")
+                f"use_fusion={use_fusion!r}: the HIP path builds plain RAFT (use_fusion=None) and the 'parallel' (CCE) "
+                "front-end; 'attention'/'conv' are selected by no shipped config (SURVEY §2.1 #8)")
         self.fusion_layer = None
         self.use_fusion = use_fusion
         self.freeze_flownet = freeze_flownet
         self.cfg = cfg
+        self._table = None
+        if use_fusion is None:
+            # ff_raft.py:124-132: plain RAFT on the images alone; abandon_fnet, fuse_cnet, fusion_channels and
+            # freeze_flownet are not read
+            self.mask_modal = None
+            self.flow_net = RAFT(in_channels=3, small=raft_small, dropout=dropout, alternate_corr=alternate_corr)
+            if pretrain is not None:
+                self.load_state_dict(torch.load(pretrain), strict=True)
+                print("Load pretrained model from {}".format(pretrain))
+            if load_raft is not None:
+                self.flow_net.load_model(load_raft, flag="all")
+                print("Load all flow net.")
+            return
         modal = getattr(cfg.TRAIN, "MASK_MODAL", "point")
         if modal not in ("point", "frame") and modal not in MASK_MODES:
             raise ValueError(f"MASK_MODAL={modal!r} is not one of point/frame/neighborG/neighborE/context")
         self.mask_modal = modal
-        self._table = None
         self.flow_net = RAFT(in_channels=fusion_channels, small=raft_small, dropout=dropout,
                              alternate_corr=alternate_corr, abandon_fnet=abandon_fnet,
                              inside_fusion="parallel", fuse_cnet=fuse_cnet, cfg=cfg)
@@ -96,11 +108,12 @@ class FF_RAFT_FUSION(nn.Module):
         self.invalidate_packed()
         return super().train(mode)
 
-    def forward(self, image1, image2, mask1, mask2, raft_iters=12, flow_init=None, test_mode=False):
+    def forward(self, image1, image2, mask1=None, mask2=None, raft_iters=12, flow_init=None, test_mode=False):
         b, c, h, w = image1.shape
-        assert mask1.shape[1] == 1  # ff_raft.py:34
         if h % 8 or w % 8:
             raise ValueError("H and W must be multiples of 8 (pad with InputPadder as the reference's callers do)")
+        modal = self.mask_modal
+        assert modal is None or mask1.shape[1] == 1  # ff_raft.py:34
         # ff_raft.py:31-38 + :142-145 fused into one NCHW->NHWC4 pass per input;
         # 'point' mode ignores the caller's mask2 and uses a constant 255 plane.
         # (both frames - and both masks - into the halves of one buffer: the feature encoder takes them as one batch of 2B
@@ -108,8 +121,9 @@ class FF_RAFT_FUSION(nn.Module):
         i12 = ops.empty_nhwc(2 * b, h, w, 4, image1)
         i1 = ops.prep_input(image1, b, h, w, image1, out=i12[:b])
         i2 = ops.prep_input(image2, b, h, w, image1, out=i12[b:])
-        modal = self.mask_modal
-        if modal == "point":
+        if modal is None:                           # plain RAFT (ff_raft.py:147-158): the masks are never read
+            m1 = m2 = None
+        elif modal == "point":
             m12 = ops.empty_nhwc(2 * b, h, w, 4, image1)
             m1 = ops.prep_input(mask1, b, h, w, image1, out=m12[:b])
             m2 = ops.prep_input(None, b, h, w, image1, fill=255.0, out=m12[b:])

@@ -1,11 +1,11 @@
-"""RAFT graph on the HIP path (raft.py:40-236, the 'parallel' inside-fusion build)."""
+"""RAFT graph on the HIP path (raft.py:40-236): plain RAFT (inside_fusion=None) and the 'parallel' inside-fusion build."""
 import os
 
 import torch
 import torch.nn as nn
 
 from . import _hip, cce, corr_block, fn, ops, train_loop
-from .cce import BasicParallelFusionLayer, train_streams
+from .cce import BasicEncoder, BasicParallelFusionLayer, train_streams
 from .corr_block import AlternateCorrBlock, CorrBlock
 from .ops import ACT_RELU, ACT_TANH
 from .update_block import BasicUpdateBlock, split_activations
@@ -21,10 +21,11 @@ class RAFT(nn.Module):
     def __init__(self, in_channels=3, small=False, dropout=0., alternate_corr=False, abandon_fnet=False,
                  inside_fusion=None, fuse_cnet=False, cfg=None):
         super().__init__()
-        if small or abandon_fnet or inside_fusion != "parallel" or not fuse_cnet:
+        if small or abandon_fnet or inside_fusion not in (None, "parallel"):
             raise NotImplementedError(
-                "the HIP path builds the configuration every shipped FF-RAFT experiment uses: "
-                "small=False, inside_fusion='parallel', fuse_cnet=True (SURVEY §2.1)")
+                f"RAFT(small={small}, abandon_fnet={abandon_fnet}, inside_fusion={inside_fusion!r}): the HIP path builds "
+                "small=False without abandon_fnet, with inside_fusion=None (plain RAFT: BasicEncoder fnet and cnet) or "
+                "'parallel' (CCE fnet; CCE cnet with fuse_cnet=True, BasicEncoder cnet with fuse_cnet=False)")
         self.small, self.abandon_fnet, self.inside_fusion, self.fuse_cnet, self.cfg = small, abandon_fnet, inside_fusion, fuse_cnet, cfg
         self.hidden_dim = hdim = 128
         self.context_dim = cdim = 128
@@ -38,9 +39,17 @@ class RAFT(nn.Module):
         self._alt_warned = False
         # storage type of the correlation pyramid: None = $FF_CORR_PYRAMID or "fp32"; "fp16" = BASELINE configs[4]
         self.corr_pyramid_dtype = None
-        mc = cfg.TRAIN.MASK_CHANNEL
-        self.fnet = BasicParallelFusionLayer(3, mc, output_dim=256, norm_fn="instance", dropout=dropout, cfg=cfg)
-        self.cnet = BasicParallelFusionLayer(3, mc, output_dim=hdim + cdim, norm_fn="batch", dropout=dropout, cfg=cfg)
+        # raft.py:92-101; cfg is read by the CCE only
+        if inside_fusion is None:
+            self.fnet = BasicEncoder(in_channels, output_dim=256, norm_fn="instance", dropout=dropout)
+            self.cnet = BasicEncoder(in_channels, output_dim=hdim + cdim, norm_fn="batch", dropout=dropout)
+        else:
+            mc = cfg.TRAIN.MASK_CHANNEL
+            self.fnet = BasicParallelFusionLayer(3, mc, output_dim=256, norm_fn="instance", dropout=dropout, cfg=cfg)
+            if fuse_cnet:
+                self.cnet = BasicParallelFusionLayer(3, mc, output_dim=hdim + cdim, norm_fn="batch", dropout=dropout, cfg=cfg)
+            else:
+                self.cnet = BasicEncoder(3, output_dim=hdim + cdim, norm_fn="batch", dropout=dropout)
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=hdim)
         # the always-on range guard's memory of this model (ops.guard_*): running max|x| of the two guarded encoder outputs, and
         # the sticky repair - the context features' convolutions on the exact-fp32 route
@@ -65,9 +74,10 @@ class RAFT(nn.Module):
                 model_dict.pop(k)
             strict = False
         self.load_state_dict(model_dict, strict=strict)
-        if flag == "all" and self.cfg.MODEL.LOAD_MODULE_TO_BRANCH:
-            self.fnet.copy_to_branch()
-            self.cnet.copy_to_branch()
+        if flag == "all" and self.inside_fusion == "parallel" and self.cfg.MODEL.LOAD_MODULE_TO_BRANCH:
+            for enc in (self.fnet, self.cnet):
+                if isinstance(enc, BasicParallelFusionLayer):     # (a BasicEncoder cnet has no branch)
+                    enc.copy_to_branch()
 
     # -- forward ------------------------------------------------------------
     def forward(self, image1, image2, mask1=None, mask2=None, iters=12, flow_init=None, upsample=True,
@@ -111,8 +121,11 @@ class RAFT(nn.Module):
                 join = torch.cuda.Event()
                 join.record(self._enc_stream)
             for t in (image1, mask1):
-                t.record_stream(self._enc_stream)
-        f12 = self.fnet(ops.cat_batch(image1, image2), ops.cat_batch(mask1, mask2))
+                if t is not None:
+                    t.record_stream(self._enc_stream)
+        # plain RAFT's encoders read no masks (raft.py:186, :204)
+        m12 = ops.cat_batch(mask1, mask2) if isinstance(self.fnet, BasicParallelFusionLayer) else None
+        f12 = self.fnet(ops.cat_batch(image1, image2), m12)
         fmap1, fmap2 = f12[:b], f12[b:]
         self.fmap = fmap1
         corr_fn = self._corr_block(fmap1, fmap2, fused_train)      # (before the context encoder's join: it overlaps that stream)
