@@ -106,6 +106,7 @@ _SIGS = {
     "ff_range_probe": [_fp, C.c_int, _ll, C.c_int, _fp, _fp],
     "ff_split_copy": [_fp, C.c_int, _fp, C.c_int, _ll, C.c_int, C.c_int, C.c_int, _fp],
     "ff_coords_init": [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp],
+    "ff_forward_interpolate": [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],
@@ -168,7 +169,8 @@ _SIGS = {
     "ff_scale_add_bwd": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int,
                          C.c_int, _fp],
 }
-EXPORTS = sorted(list(_SIGS) + ["ff_last_error", "ff_abi_version", "ff_corr_plane_elems", "ff_conv2d_splitk_hint", "ff_conv2d_stats_parts", "ff_fusion_pair_tile"])
+EXPORTS = sorted(list(_SIGS) + ["ff_last_error", "ff_abi_version", "ff_corr_plane_elems", "ff_conv2d_splitk_hint", "ff_conv2d_stats_parts", "ff_fusion_pair_tile",
+                                 "ff_forward_interpolate_ws"])
 
 ABI_VERSION = 7      # include/focusflow_hip.h: FF_ABI_VERSION
 _lib = None
@@ -219,6 +221,8 @@ def load():
     lib.ff_conv2d_splitk_hint.argtypes = [C.POINTER(FFConvParams)]
     lib.ff_fusion_pair_tile.restype = C.c_int
     lib.ff_fusion_pair_tile.argtypes = [C.c_int]
+    lib.ff_forward_interpolate_ws.restype = C.c_int
+    lib.ff_forward_interpolate_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_conv2d_stats_parts.restype = C.c_int
     lib.ff_conv2d_stats_parts.argtypes = [C.POINTER(FFConvParams)]
     got = lib.ff_abi_version()

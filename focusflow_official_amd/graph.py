@@ -13,18 +13,41 @@ class GraphedForward:
     """Capture `model(image1, image2, mask1, mask2, raft_iters, test_mode=True)` for fixed shapes.
 
     Call it with new inputs of the same shape: they are copied into the captured input buffers, the
-    graph is replayed and the (static) output tensors are returned — valid until the next call."""
+    graph is replayed and the (static) output tensors are returned — valid until the next call.
 
-    def __init__(self, model, example_inputs, raft_iters=12, warmup=3):
+    flow_init=True: the capture passes the static (B,2,H/8,W/8) buffer `self.flow_init` to the model as its flow_init
+    (raft.py:211-212).  It starts at zero, which is bit-identical to no flow_init (x + 0.0f); `__call__(..., flow_init=t)`
+    copies t into it and `reset()` zeroes it.
+    warm_start=True (implies flow_init): ops.forward_interpolate(flow_low, out=self.flow_init) is captured behind the
+    forward on the main stream, so every replay leaves the next replay's initialisation in place without the host seeing
+    it - consecutive pairs of a video; `reset()` at a sequence boundary."""
+
+    def __init__(self, model, example_inputs, raft_iters=12, warmup=3, flow_init=False, warm_start=False):
         if model.training:
             raise ValueError("capture the eval-mode forward (training mutates BatchNorm buffers and the tape)")
         self.model, self.iters = model, raft_iters
         self.static_in = [t.clone() if t is not None else None for t in example_inputs]    # (plain RAFT: masks may be None)
+        self.warm_start = bool(warm_start)
+        self.flow_init = None
+        if flow_init or warm_start:
+            b, _, h, w = self.static_in[0].shape
+            self.flow_init = torch.zeros((b, 2, h // 8, w // 8), dtype=torch.float32, device=self.static_in[0].device)
+
+        def step():
+            if self.flow_init is None:      # (the call as it always was)
+                return model(*self.static_in, raft_iters=raft_iters, test_mode=True)
+            out = model(*self.static_in, raft_iters=raft_iters, flow_init=self.flow_init, test_mode=True)
+            if self.warm_start:
+                ops.forward_interpolate(out[0], out=self.flow_init)
+            return out
+
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(warmup):      # packs weights, sets kernel attributes, warms the allocator
-                model(*self.static_in, raft_iters=raft_iters, test_mode=True)
+                step()
+            if self.flow_init is not None:
+                self.flow_init.zero_()       # (the warm-up forwards of a warm start left their own initialisation there)
         torch.cuda.current_stream().wait_stream(side)
         ops.guard_check(sync=True)          # the warm-up forwards decided the routes (exact context convolutions or not): capture those
         # the always-on range guard inside a graph: the probes go to a static pair of words (zeroed by a captured fill), which
@@ -35,19 +58,29 @@ class GraphedForward:
         self.graph = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(self.graph), torch.no_grad():
-                self.out = model(*self.static_in, raft_iters=raft_iters, test_mode=True)
+                self.out = step()
         finally:
             st["capture_words"] = None
 
-    def __call__(self, *inputs):
+    def __call__(self, *inputs, flow_init=None):
         for dst, src in zip(self.static_in, inputs):
             if dst is not None and dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
+        if flow_init is not None:
+            if self.flow_init is None:
+                raise ValueError("this graph was captured without a flow_init input: GraphedForward(..., flow_init=True)")
+            if flow_init.data_ptr() != self.flow_init.data_ptr():
+                self.flow_init.copy_(flow_init)
         ops.guard_check()                   # (raises if an earlier replay left the split formats' range)
         self.graph.replay()
         if self._guard_words is not None:
             ops.guard_queue(self._guard_words, "GraphedForward replay", getattr(self.model, "flow_net", None))
         return self.out
+
+    def reset(self):
+        """Back to a cold start: zero the flow_init buffer (a sequence boundary)."""
+        if self.flow_init is not None:
+            self.flow_init.zero_()
 
     def check_range(self):
         """Wait for the replays issued so far and raise if one of them left the fp16-split formats' range (ops: the always-on guard)."""

@@ -961,6 +961,31 @@ def coords_init(b, h, w, like: Tensor, flow_init: Optional[Tensor] = None) -> Te
     return coords
 
 
+def forward_interpolate(flow: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """utils.forward_interpolate (utils.py:26-54) on the device: the 1/8-resolution flow of one pair -> the flow_init of the
+    next.  flow: (2,H,W) or (B,2,H,W), any strides; out: a contiguous tensor of the same shape (default: a new one; may be
+    `flow` itself).  Bit-equal to an fp64 brute-force nearest neighbour with ties to the lowest source index; a sample of
+    which no vector lands gives zeros where scipy gives NaN (csrc/warm_start.hip)."""
+    _require_gpu(flow)
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise _hip.FocusFlowHipError(f"forward_interpolate: (2,H,W) or (B,2,H,W) expected, got {tuple(flow.shape)}")
+    src = flow.contiguous()
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _require_gpu(out)
+        if out.shape != flow.shape or not out.is_contiguous():
+            raise _hip.FocusFlowHipError(f"forward_interpolate: out must be contiguous {tuple(flow.shape)}, got {tuple(out.shape)} strides {out.stride()}")
+    b = src.shape[0] if src.dim() == 4 else 1
+    h, w = src.shape[-2:]
+    nbytes = _hip.load().ff_forward_interpolate_ws(b, h, w)
+    if nbytes <= 0:
+        raise _hip.FocusFlowHipError(f"forward_interpolate: shape {tuple(flow.shape)} is not supported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+    _hip.call("ff_forward_interpolate", _p(src), _p(out), _p(ws), b, h, w, _stream())
+    return out
+
+
 def coords_step(coords1: Tensor, delta: Optional[Tensor], flow4: Optional[Tensor], slot: Optional[Tensor]):
     b, h, w, _ = coords1.shape
     _hip.call("ff_coords_step", _p(coords1), _p(delta), _ld(delta) if delta is not None else 0, _p(flow4), _p(slot),

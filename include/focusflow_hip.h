@@ -57,7 +57,8 @@ const char* ff_last_error(void);
  *                layers of the update block); + ff_split_copy; FF_EP_MOTION_TAIL
  *   6 (round 4): entry points only: ff_fusion_pair_fwd / ff_fusion_pair_tile (FFFusionPair)
  *   7 (round 5): entry points only: ff_gru_bwd_blend / _rh / _out, ff_sum_stack, ff_upsample_flow_bwd_ex (the recorded
- *                update loop's backward), ff_gru_pass_rec */
+ *                update loop's backward), ff_gru_pass_rec
+ *   7 (unchanged): entry points only: ff_forward_interpolate / ff_forward_interpolate_ws (warm start of video inference) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -355,6 +356,18 @@ int ff_split_copy(const float* src, int src_ld, float* dst, int dst_ld, long lon
 int ff_range_probe(const float* x, int ld, long long npix, int C, unsigned int* word, void* stream);
 /* coords_grid (utils.py:74-77): coords[b][y][x] = (x, y) (+ flow_init NHWC2 if given) */
 int ff_coords_init(float* coords, const float* flow_init_nchw, int B, int H, int W, void* stream);
+/* forward_interpolate (core/utils/utils.py:26-54), the producer of flow_init (raft.py:211-212) for the next frame pair of a
+ * video, batched and device to device: flow and out are (B,2,H,W) NCHW fp32 (the layout of flow_low and of ff_coords_init's
+ * flow_init); out may alias flow.  Source pixel (x0, y0) lands at (x0 + dx, y0 + dy), evaluated in fp64 as numpy does; it is
+ * kept iff 0 < x1 < W and 0 < y1 < H (strict; NaN / inf drop out); every grid pixel copies both components of the kept vector
+ * whose landing point is nearest in fp64 squared distance, ties going to the lowest row-major source index (the reduction
+ * key is (d2, index): deterministic, also under graph replay).  ONE deliberate difference to scipy.griddata: a sample of which
+ * no vector lands gives zeros (a cold start), not NaN.  Enqueues only (capturable); ws: ff_forward_interpolate_ws bytes,
+ * 16-byte aligned, contents need no initialisation.  H, W <= 32767.
+ *   ff_forward_interpolate_ws   bytes of workspace for (B, H, W); 0 = shape not supported.  A plain return value, not a
+ *                               status.  Does not launch anything. */
+int ff_forward_interpolate_ws(int B, int H, int W);
+int ff_forward_interpolate(const float* flow_nchw, float* out_nchw, void* ws, int B, int H, int W, void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
