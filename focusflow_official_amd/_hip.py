@@ -107,6 +107,7 @@ _SIGS = {
     "ff_split_copy": [_fp, C.c_int, _fp, C.c_int, _ll, C.c_int, C.c_int, C.c_int, _fp],
     "ff_coords_init": [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp],
     "ff_forward_interpolate": [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp],
+    "ff_good_features": [_fp, C.c_int, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp, _fp, _fp, _fp, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],
@@ -170,7 +171,7 @@ _SIGS = {
                          C.c_int, _fp],
 }
 EXPORTS = sorted(list(_SIGS) + ["ff_last_error", "ff_abi_version", "ff_corr_plane_elems", "ff_conv2d_splitk_hint", "ff_conv2d_stats_parts", "ff_fusion_pair_tile",
-                                 "ff_forward_interpolate_ws"])
+                                 "ff_forward_interpolate_ws", "ff_good_features_ws"])
 
 ABI_VERSION = 7      # include/focusflow_hip.h: FF_ABI_VERSION
 _lib = None
@@ -223,6 +224,8 @@ def load():
     lib.ff_fusion_pair_tile.argtypes = [C.c_int]
     lib.ff_forward_interpolate_ws.restype = C.c_int
     lib.ff_forward_interpolate_ws.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.ff_good_features_ws.restype = C.c_int
+    lib.ff_good_features_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_conv2d_stats_parts.restype = C.c_int
     lib.ff_conv2d_stats_parts.argtypes = [C.POINTER(FFConvParams)]
     got = lib.ff_abi_version()

@@ -9,6 +9,14 @@ import torch
 from . import ops
 
 
+def require_mask_reader(model):
+    """keypoints= makes sense only for a model whose forward reads mask1: FF_RAFT_FUSION with a fusion branch."""
+    if getattr(model, "mask_modal", None) is None:
+        raise ValueError(f"keypoints= given to {type(model).__name__}, which reads no key-point mask here: plain RAFT (use_fusion=None) "
+                         "takes no mask, and models other than FF_RAFT_FUSION are not supported by these session classes "
+                         "(give FF-PWC the detector's mask like any other mask)")
+
+
 class GraphedForward:
     """Capture `model(image1, image2, mask1, mask2, raft_iters, test_mode=True)` for fixed shapes.
 
@@ -20,13 +28,21 @@ class GraphedForward:
     copies t into it and `reset()` zeroes it.
     warm_start=True (implies flow_init): ops.forward_interpolate(flow_low, out=self.flow_init) is captured behind the
     forward on the main stream, so every replay leaves the next replay's initialisation in place without the host seeing
-    it - consecutive pairs of a video; `reset()` at a sequence boundary."""
+    it - consecutive pairs of a video; `reset()` at a sequence boundary.
+    keypoints=det (keypoints.GoodFeatures): det(static image1, out=self.mask1) is captured in front of the model, so every
+    replay computes the key-point mask of the frame it was given; example_inputs[2] may then be None, and `__call__` takes
+    None for mask1 and refuses a tensor there (either the graph detects or the caller supplies)."""
 
-    def __init__(self, model, example_inputs, raft_iters=12, warmup=3, flow_init=False, warm_start=False):
+    def __init__(self, model, example_inputs, raft_iters=12, warmup=3, flow_init=False, warm_start=False, keypoints=None):
         if model.training:
             raise ValueError("capture the eval-mode forward (training mutates BatchNorm buffers and the tape)")
         self.model, self.iters = model, raft_iters
         self.static_in = [t.clone() if t is not None else None for t in example_inputs]    # (plain RAFT: masks may be None)
+        self.keypoints = keypoints
+        if keypoints is not None:
+            require_mask_reader(model)
+            b, _, h, w = self.static_in[0].shape
+            self.static_in[2] = torch.zeros((b, 1, h, w), dtype=torch.float32, device=self.static_in[0].device)
         self.warm_start = bool(warm_start)
         self.flow_init = None
         if flow_init or warm_start:
@@ -34,6 +50,8 @@ class GraphedForward:
             self.flow_init = torch.zeros((b, 2, h // 8, w // 8), dtype=torch.float32, device=self.static_in[0].device)
 
         def step():
+            if keypoints is not None:
+                keypoints(self.static_in[0], out=self.static_in[2])
             if self.flow_init is None:      # (the call as it always was)
                 return model(*self.static_in, raft_iters=raft_iters, test_mode=True)
             out = model(*self.static_in, raft_iters=raft_iters, flow_init=self.flow_init, test_mode=True)
@@ -62,8 +80,17 @@ class GraphedForward:
         finally:
             st["capture_words"] = None
 
+    @property
+    def mask1(self):
+        """The static mask1 buffer: with keypoints=, the mask of the last replay's image1."""
+        return self.static_in[2]
+
     def __call__(self, *inputs, flow_init=None):
-        for dst, src in zip(self.static_in, inputs):
+        if self.keypoints is not None and len(inputs) > 2 and inputs[2] is not None:
+            raise ValueError("this graph detects mask1 itself (keypoints=...): pass None for mask1, or capture without a detector and supply it")
+        for k, (dst, src) in enumerate(zip(self.static_in, inputs)):
+            if self.keypoints is not None and k == 2:
+                continue
             if dst is not None and dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         if flow_init is not None:

@@ -986,6 +986,45 @@ def forward_interpolate(flow: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+def good_features_ws(b: int, h: int, w: int) -> int:
+    """Bytes of workspace ff_good_features needs for (B, H, W); 0: the shape is not supported."""
+    return _hip.load().ff_good_features_ws(b, h, w)
+
+
+def good_features(image: Tensor, max_corners: int = 500, quality_level: float = 0.01, min_distance: int = 10,
+                  out: Optional[Tensor] = None, return_points: bool = False, ws: Optional[Tensor] = None):
+    """Shi-Tomasi key points as a mask (csrc/keypoints.hip): what scripts/maskGenerate.py makes offline with
+    cv.goodFeaturesToTrack(img, 500, 0.01, 10).  image: (B,3,H,W) R,G,B or (B,1,H,W) fp32 in [0,255], any strides with a
+    dense innermost dimension; out: a contiguous (B,1,H,W) fp32 tensor (default: a new one).  -> mask (255 at key points,
+    0 elsewhere), or (mask, points (B,max_corners,2) int32 [x, y] in acceptance order and -1 beyond the count, count (B)
+    int32).  ws: a uint8 device tensor of good_features_ws(B, H, W) bytes to work in (default: a new one per call).
+    Exact: equal to the integer / fp64 definition bit for bit.  Enqueues only, so it can be captured."""
+    _require_gpu(image)
+    if image.dim() != 4:
+        raise _hip.FocusFlowHipError(f"good_features: (B,1,H,W) or (B,3,H,W) expected, got {tuple(image.shape)}")
+    b, c, h, w = image.shape
+    if w > 1 and image.stride(3) != 1:
+        image = image.contiguous()
+    if out is None:
+        out = torch.empty((b, 1, h, w), dtype=torch.float32, device=image.device)
+    else:
+        _require_gpu(out)
+        if out.shape != (b, 1, h, w) or not out.is_contiguous():
+            raise _hip.FocusFlowHipError(f"good_features: out must be contiguous {(b, 1, h, w)}, got {tuple(out.shape)} strides {out.stride()}")
+    points = count = None
+    if return_points and max_corners >= 1:
+        points = torch.empty((b, max_corners, 2), dtype=torch.int32, device=image.device)
+        count = torch.empty((b,), dtype=torch.int32, device=image.device)
+    nbytes = good_features_ws(b, h, w)
+    if ws is None:
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=image.device)      # (an unsupported shape is refused by the call itself, with its reason)
+    elif ws.dtype != torch.uint8 or ws.device != image.device or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise _hip.FocusFlowHipError(f"good_features: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {image.device}")
+    _hip.call("ff_good_features", _p(image), c, image.stride(0), image.stride(1), image.stride(2), b, h, w, int(max_corners),
+              float(quality_level), int(min_distance), _p(ws), _p(out), _p(points), _p(count), _stream())
+    return (out, points, count) if return_points else out
+
+
 def coords_step(coords1: Tensor, delta: Optional[Tensor], flow4: Optional[Tensor], slot: Optional[Tensor]):
     b, h, w, _ = coords1.shape
     _hip.call("ff_coords_step", _p(coords1), _p(delta), _ld(delta) if delta is not None else 0, _p(flow4), _p(slot),

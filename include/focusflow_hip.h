@@ -58,7 +58,8 @@ const char* ff_last_error(void);
  *   6 (round 4): entry points only: ff_fusion_pair_fwd / ff_fusion_pair_tile (FFFusionPair)
  *   7 (round 5): entry points only: ff_gru_bwd_blend / _rh / _out, ff_sum_stack, ff_upsample_flow_bwd_ex (the recorded
  *                update loop's backward), ff_gru_pass_rec
- *   7 (unchanged): entry points only: ff_forward_interpolate / ff_forward_interpolate_ws (warm start of video inference) */
+ *   7 (unchanged): entry points only: ff_forward_interpolate / ff_forward_interpolate_ws (warm start of video inference)
+ *   7 (unchanged): entry points only: ff_good_features / ff_good_features_ws (key-point masks on the device) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -368,6 +369,25 @@ int ff_coords_init(float* coords, const float* flow_init_nchw, int B, int H, int
  *                               status.  Does not launch anything. */
 int ff_forward_interpolate_ws(int B, int H, int W);
 int ff_forward_interpolate(const float* flow_nchw, float* out_nchw, void* ws, int B, int H, int W, void* stream);
+/* Shi-Tomasi key points, the `goodfeature` mask type (scripts/maskGenerate.py:11-30: cv.goodFeaturesToTrack(img, 500, 0.01,
+ * 10), block size 3, Sobel aperture 3, minimum eigenvalue).  image: B samples of `channels` (1 = gray, 3 = R,G,B) planes of
+ * H x W fp32 values in [0,255]; element (b, c, y, x) is image[b ld_b + c ld_c + y ld_row + x] (strides in elements: a crop of a
+ * wider buffer needs no copy).  Every channel is rounded half-even and clamped to 0..255; gray = (4899 R + 9617 G + 1868 B +
+ * 8192) >> 14; 3x3 Sobel and the 3x3 sums of its products in integers with reflect-101 borders; the smaller eigenvalue in fp64;
+ * a pixel survives above max * quality_level (maximum per sample); candidates are the surviving 3x3 maxima off the outermost
+ * ring; they are walked by descending eigenvalue, ties by ascending y W + x, and accepted unless an accepted point lies at
+ * dx^2 + dy^2 < min_distance^2, until max_corners are accepted.  Every step is exact, so the result has no tolerance.
+ *   mask    (B,1,H,W) contiguous: 255 at accepted points, 0 elsewhere
+ *   points  (B, max_corners, 2) int32 [x, y] in acceptance order, rows beyond the count -1; may be null
+ *   count   (B) int32; may be null
+ *   ws      ff_good_features_ws bytes, 16-byte aligned, contents need no initialisation
+ * Refused (FF_EINVAL): channels not 1 or 3, H or W < 3, max_corners < 1, quality_level outside (0, 1], min_distance outside
+ * 0 .. 32.  Enqueues only (capturable): ten launches, whatever the image holds.
+ *   ff_good_features_ws   bytes of workspace for (B, H, W); 0 = shape not supported.  A plain return value, not a status. */
+int ff_good_features_ws(int B, int H, int W);
+int ff_good_features(const float* image, int channels, long long ld_b, long long ld_c, long long ld_row, int B, int H, int W,
+                     int max_corners, double quality_level, int min_distance, void* ws, float* mask, int* points, int* count,
+                     void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
