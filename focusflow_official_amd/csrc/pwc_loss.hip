@@ -13,8 +13,12 @@
 
 namespace {
 
+// Source coordinate of F.interpolate(bilinear, align_corners=False).  One explicit fma: ATen rounds (dst + 0.5) * scale - 0.5
+// once, and so must this, whatever -ffp-contract says.  Rounding the product first moves the coordinate across an integer
+// at a few size pairs (33 -> 13 at index 6: 15.999999 fused, 16.0 unfused), and the mask is thresholded (> 0) after the
+// resize: a key point in the one source row below the crossing would turn an output pixel on or off.
 __device__ __forceinline__ float bilinear_src(int dst, float scale) {
-    const float s = ((float)dst + 0.5f) * scale - 0.5f;
+    const float s = __fmaf_rn((float)dst + 0.5f, scale, -0.5f);
     return s < 0.f ? 0.f : s;
 }
 

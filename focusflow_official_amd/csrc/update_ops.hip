@@ -248,6 +248,12 @@ __global__ void nchw_to_nhwc4_kernel(const float* __restrict__ src, int src_c, f
     }
 }
 
+// Source coordinate (dst + 0.5) * scale - 0.5 of a bilinear resize, before the clamp at 0.  One explicit fma: ATen rounds
+// it once, and so must this, whatever -ffp-contract says.  Rounding the product first moves the coordinate across an
+// integer at a few size pairs (33 -> 13 at index 6: 15.999999 fused, 16.0 unfused): harmless for an image, but the resized
+// key-point mask is thresholded (> 0) downstream, where that decides a pixel.
+__device__ __forceinline__ float resize_src(int dst, float scale) { return __fmaf_rn((float)dst + 0.5f, scale, -0.5f); }
+
 // F.interpolate(mode='bilinear', align_corners=False) from NHWC (ld) to NCHW, channel c scaled by mul[c]
 __global__ void resize_bilinear_kernel(const float* __restrict__ src, int ld, int C, int Hi, int Wi, float* __restrict__ dst,
                                        int B, int Ho, int Wo, float mul0, float mul1) {
@@ -259,7 +265,7 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ src, int ld, in
         const int y = (int)(t % Ho); t /= Ho;
         const int c = (int)(t % C);
         const long long b = t / C;
-        float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
+        float fy = resize_src(y, sy), fx = resize_src(x, sx);
         fy = fy < 0.f ? 0.f : fy;
         fx = fx < 0.f ? 0.f : fx;
         const int y0 = (int)fy, x0 = (int)fx;
@@ -284,7 +290,7 @@ __global__ void resize_to_nhwc4_kernel(const float* __restrict__ src, int src_c,
         const long long t = i / Wo;
         const int y = (int)(t % Ho);
         const long long b = t / Ho;
-        float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
+        float fy = resize_src(y, sy), fx = resize_src(x, sx);
         fy = fy < 0.f ? 0.f : fy;
         fx = fx < 0.f ? 0.f : fx;
         const int y0 = (int)fy, x0 = (int)fx;

@@ -414,14 +414,16 @@ def gaussian_box(kernel_size, sigma):
 
 
 def sequence_loss(kind, preds, flow_gt, valid, mask, gamma=0.8, max_flow=400.0, kernel_size=5, sigma=1.7, lamda=0.8):
-    """EPELoss / CPCL / MixLoss, losses.py:18-130 (kind in {'EPELoss','CPCL','MixLoss'})."""
+    """EPELoss / CPCL / MixLoss, losses.py:18-130 (kind in {'EPELoss','CPCL','MixLoss'}).  Runs in the dtype of the ground
+    truth (fp32 as the reference, or fp64: the Gaussian box keeps its fp32 table values, the weight map and its sum are
+    then formed in fp64)."""
     n = len(preds)
     mag = torch.sum(flow_gt ** 2, dim=1).sqrt()
     ok = (valid >= 0.5) & (mag < max_flow)
     if kind != "EPELoss":
-        m = (mask > 0).float()
+        m = (mask > 0).to(flow_gt.dtype)
         pad = kernel_size // 2
-        m = F.conv2d(F.pad(m, [pad, pad, pad, pad]), gaussian_box(kernel_size, sigma))
+        m = F.conv2d(F.pad(m, [pad, pad, pad, pad]), gaussian_box(kernel_size, sigma).to(flow_gt.dtype))
     loss = 0.0
     for i, pr in enumerate(preds):
         wgt = gamma ** (n - i - 1)
@@ -474,10 +476,10 @@ def init_mask(image1, image2, mask1, modal, mask_channel=3, dilate=31, kernel_si
     if modal == "frame":
         return image1.clone(), image2.clone()
     if modal == "neighborG":
-        m = F.conv2d(mask1, gaussian_box(kernel_size, kernel_sigma), padding=kernel_size // 2)
+        m = F.conv2d(mask1, gaussian_box(kernel_size, kernel_sigma).to(mask1.dtype), padding=kernel_size // 2)
         m = (m * 255 / m.max()).repeat(1, mask_channel, 1, 1)
         return m, torch.ones_like(m) * 255
-    el = ellipse_element(dilate)[None, None]
+    el = ellipse_element(dilate)[None, None].to(mask1.dtype)
     dil = F.conv2d(mask1 / 255, el, padding=dilate // 2) > 0
     if modal == "neighborE":
         m = (dil * 255).float().repeat(1, mask_channel, 1, 1)

@@ -185,3 +185,86 @@ def pwc_state_spec():
     for i, (ci, co) in enumerate(chans):
         conv(f"netRefiner.netMain.{2 * i}", co, ci, 3)
     return spec
+
+
+# ----------------------------------------------------------------------------
+# FF-PWC multi-scale losses (losses/losses.py:19-261), restated from the formulas in the header of
+# focusflow_official_amd/csrc/pwc_loss.hip.  Works in the dtype of the predictions (fp32 or fp64).  PINNED by
+# tests/golden/pwc_losses.npz (the reference's own classes, tests/golden/make_golden_pwc_losses.py) in
+# tests/test_oracle_golden.py.
+# ----------------------------------------------------------------------------
+PWC_LOSS_WEIGHTS = (0.005, 0.01, 0.02, 0.08, 0.32)
+
+
+def pwc_sparse_max_pool(t: torch.Tensor, size) -> torch.Tensor:
+    """Down-sampling of a sparse target (0 = no value): max of the positive values minus max of the negated negative ones
+    over the adaptive window."""
+    return F.adaptive_max_pool2d(t * (t > 0), size) - F.adaptive_max_pool2d(-t * (t < 0), size)
+
+
+def pwc_mask_map(mask: torch.Tensor, size) -> torch.Tensor:
+    """(B,1,H,W) key-point mask -> boolean (B,1,h,w): bilinear resize, then > 0.  Runs in the mask's own dtype: which source
+    rows a resized pixel touches depends on the rounding of the source coordinate (ATen rounds it once, in that dtype)."""
+    return F.interpolate(mask, size, mode="bilinear", align_corners=False) > 0
+
+
+def pwc_error_map(out: torch.Tensor, target: torch.Tensor, mode: str, eps: float, q: float) -> torch.Tensor:
+    """(B,2,h,w) x2 -> (B,h,w): |t - o|_2 for 'pretrain', (|t - o|_1 + eps)^q otherwise."""
+    d = target - out
+    if mode == "pretrain":
+        return torch.linalg.vector_norm(d, 2, dim=1)
+    return (d.abs().sum(1) + eps) ** q
+
+
+def pwc_real_epe(out: torch.Tensor, target: torch.Tensor, sparse=False, mode="pretrain", eps=0.01, q=0.4) -> torch.Tensor:
+    """The reported 'epe': mean error of `out` bilinearly resized to the target's size; sparse: over the pixels whose
+    target is not exactly (0, 0)."""
+    up = F.interpolate(out, target.shape[-2:], mode="bilinear", align_corners=False)
+    e = pwc_error_map(up, target, mode, eps, q)
+    if sparse:
+        e = e[~((target[:, 0] == 0) & (target[:, 1] == 0))]
+    return e.mean()
+
+
+def pwc_multiscale_loss(kind, preds, target, mask=None, sparse=False, mode="pretrain", weights=PWC_LOSS_WEIGHTS, q=0.4, eps=0.01,
+                        kernel_size=5, sigma=1.7, lamda=0.7, mask_maps=None):
+    """EPELoss / CPCL / MixLoss of FF-PWC over the pyramid `preds` (finest first) -> (loss, {'epe', 'loss'}).
+
+    Per level (b,2,h,w) with weight wgt, E the error map against the down-sampled target (area interpolation; sparse:
+    pwc_sparse_max_pool, and pixels whose pooled target is exactly (0, 0) are invalid), G the zero-padded Gaussian
+    convolution of the boolean mask map:
+        EPELoss  wgt * sum(E over valid) / b
+        CPCL     wgt * sum(E * G) / sum(G) * h*w   with E (b,h,w) and G (b,1,h,w): the product broadcasts to
+                 (b,b,h,w), every sample's errors meet every sample's mask; 0/0 when the map is empty; sparse is refused
+        MixLoss  wgt * (sum(E) + lamda * sum(E * G over valid) / sum(G) * h*w); an empty map drops the second term
+    `mask_maps`: optional boolean (b,1,h,w) maps, one per level, used instead of pwc_mask_map(mask, (h, w))."""
+    from .ffraft_ref import gaussian_box
+    if kind not in ("EPELoss", "CPCL", "MixLoss"):
+        raise ValueError(kind)
+    if kind == "CPCL" and sparse:
+        raise NotImplementedError("CPCL is defined for dense ground truth only")
+    assert len(weights) == len(preds)
+    dtype = preds[0].dtype
+    target = target.to(dtype)
+    loss = 0.0
+    for lvl, (out, wgt) in enumerate(zip(preds, weights)):
+        b, _, h, w = out.shape
+        t = pwc_sparse_max_pool(target, (h, w)) if sparse else F.interpolate(target, (h, w), mode="area")
+        e = pwc_error_map(out, t, mode, eps, q)
+        valid = ~((t[:, 0] == 0) & (t[:, 1] == 0)) if sparse else torch.ones_like(e, dtype=torch.bool)
+        if kind == "EPELoss":
+            loss = loss + wgt * (e * valid).sum() / b
+            continue
+        m = mask_maps[lvl] if mask_maps is not None else pwc_mask_map(mask, (h, w))
+        assert m.dtype == torch.bool and tuple(m.shape) == (b, 1, h, w)
+        pad = kernel_size // 2
+        g = F.conv2d(F.pad(m.to(dtype), [pad, pad, pad, pad]), gaussian_box(kernel_size, sigma).to(dtype))
+        if kind == "CPCL":
+            loss = loss + wgt * (e * g).sum() / g.sum() * (h * w)          # (b,h,w) * (b,1,h,w) -> (b,b,h,w)
+        else:
+            term = e.sum()
+            if m.any():
+                term = term + lamda * (e * valid * g[:, 0]).sum() / g.sum() * (h * w)
+            loss = loss + wgt * term
+    epe = pwc_real_epe(preds[0].detach(), target, sparse, mode, eps, q)
+    return loss, {"epe": epe, "loss": loss.detach() if torch.is_tensor(loss) else loss}

@@ -237,6 +237,70 @@ def test_loss_oracle_matches_reference(kind):
         np.testing.assert_allclose(p.grad[:, :, ::3, ::3].numpy(), g[f"{kind}:g{i}"], rtol=1e-5, atol=1e-9)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("kind", ["EPELoss", "CPCL", "MixLoss"])
+def test_loss_oracle_runs_in_fp64(kind, dtype):
+    """orc.sequence_loss with fp64 predictions and ground truth (the reference of tests/test_loss_kernels.py): same vectors,
+    and the gradients come back in the predictions' dtype."""
+    g = load_golden("losses")
+    preds, gt, valid, mask = orc.loss_inputs()
+    preds = [p.to(dtype).requires_grad_(True) for p in preds]
+    loss, metrics = orc.sequence_loss(kind, preds, gt.to(dtype), valid, mask, **LOSS_KINDS[kind])
+    loss.backward()
+    assert loss.dtype == dtype and all(p.grad.dtype == dtype for p in preds)
+    assert abs(loss.item() - g[kind + ":loss"][0]) < 1e-6 * max(1, abs(g[kind + ":loss"][0]))
+    assert abs(metrics["epe"] - g[kind + ":epe"][0]) < 1e-5
+    for i, p in enumerate(preds):
+        np.testing.assert_allclose(p.grad[:, :, ::3, ::3].numpy(), g[f"{kind}:g{i}"], rtol=1e-5, atol=1e-9)
+
+
+PWC_LOSS_TAGS = ["EPELoss_pretrain_k1", "EPELoss_finetune_k1", "CPCL_pretrain_k1", "CPCL_pretrain_k5", "CPCL_finetune_k1",
+                 "CPCL_finetune_k5", "MixLoss_pretrain_k1", "MixLoss_pretrain_k5", "MixLoss_finetune_k1", "MixLoss_finetune_k5",
+                 "sparse_EPELoss_pretrain_k1", "sparse_EPELoss_finetune_k1", "sparse_MixLoss_pretrain_k5",
+                 "sparse_MixLoss_finetune_k5"]
+
+
+def pwc_loss_tag(tag):
+    """'[sparse_]<loss>_<mode>_k<n>' -> (sparse, keyword arguments of pwc_ref.pwc_multiscale_loss)."""
+    parts = tag.split("_")
+    sparse = parts[0] == "sparse"
+    kind, mode, k = parts[-3:]
+    ks, sigma = {"k1": (1, 0.01), "k3": (3, 0.8), "k5": (5, 1.7)}[k]
+    return sparse, dict(kind=kind, mode=mode, kernel_size=ks, sigma=sigma, lamda=0.7, q=0.4, eps=0.01)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("tag", PWC_LOSS_TAGS)
+def test_pwc_loss_oracle_matches_reference(tag, dtype):
+    """pwc_ref.pwc_multiscale_loss vs vectors from the reference's own FF-PWC loss classes (tests/golden/
+    make_golden_pwc_losses.py): every tag stored - loss, 'epe' and the five gradients - with the tolerances
+    tests/test_hip_losses.py applies to the same file.  The mask stays fp32 in both runs (the resize that is thresholded)."""
+    from oracle import pwc_ref
+    g = load_golden("pwc_losses")
+    assert sorted(k[:-5] for k in g if k.endswith("_loss")) == sorted(PWC_LOSS_TAGS)      # every stored tag is checked
+    sparse, kw = pwc_loss_tag(tag)
+    target = torch.from_numpy(g["sparse_target" if sparse else "target"]).to(dtype)
+    preds = [torch.from_numpy(g[f"pred{i}"]).to(dtype).requires_grad_(True) for i in range(5)]
+    loss, res = pwc_ref.pwc_multiscale_loss(preds=preds, target=target, mask=torch.from_numpy(g["mask"]), sparse=sparse, **kw)
+    loss.backward()
+    want_loss, want_epe = g[tag + "_loss"]
+    assert loss.dtype == dtype
+    assert abs(loss.item() - want_loss) < 2e-5 * abs(want_loss), (loss.item(), want_loss)
+    assert abs(float(res["epe"]) - want_epe) < 2e-5 * abs(want_epe)
+    for i, p in enumerate(preds):
+        want = g[f"{tag}_grad{i}"]
+        np.testing.assert_allclose(p.grad.numpy(), want, rtol=2e-4, atol=2e-6 * float(np.abs(want).max()), err_msg=f"level {i}")
+
+
+def test_pwc_loss_oracle_refuses_sparse_cpcl():
+    from oracle import pwc_ref
+    g = load_golden("pwc_losses")
+    assert int(g["sparse_CPCL_raises"][0]) == 1
+    preds = [torch.from_numpy(g[f"pred{i}"]) for i in range(5)]
+    with pytest.raises(NotImplementedError):
+        pwc_ref.pwc_multiscale_loss("CPCL", preds, torch.from_numpy(g["sparse_target"]), torch.from_numpy(g["mask"]), sparse=True)
+
+
 @pytest.mark.parametrize("ft", ["1x1conv", "concat"])
 def test_ffpwc_restatement_matches_reference_layers(ft):
     """FF_PWCNET (ff_pwcnet.py:113-434) restated in oracle/pwc_ref.py vs vectors from the reference's own module run
