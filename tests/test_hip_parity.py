@@ -79,8 +79,8 @@ CONV_CASES = [
     ([128, 128, 128], 128, 5, 1, 1, (2, 0), 1, 16, 24, 3, False),  # convq vertical, tanh
     ([256], 2, 3, 3, 1, (1, 1), 1, 16, 24, 0, False),       # flow head conv2 (Cout 2)
     ([256], 576, 1, 1, 1, (0, 0), 1, 16, 24, 0, False),     # mask head
-    ([128], 128, 3, 3, 1, (1, 1), 8, 48, 64, 1, False),     # big-M: 128x128 tiles
-    ([64], 64, 3, 3, 1, (1, 1), 2, 96, 128, 1, False),      # 128x64 tiles
+    ([128], 128, 3, 3, 1, (1, 1), 8, 48, 64, 1, False),     # big-M (24576): fp32 still the 64x64 tile (192 / 384 blocks of 128 rows, under 200 / 400); f16x3 conv_dma.hip 8-row tiles, f16 conv_patch.hip 4-row
+    ([64], 64, 3, 3, 1, (1, 1), 2, 96, 128, 1, False),      # fp32 the 64x64 tile as well (192 blocks of 128x64); both split formats conv_patch.hip 4-row tiles (the 128-row tiles: test_conv_routes.py)
 ]
 
 
