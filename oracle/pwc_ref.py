@@ -26,8 +26,9 @@ def cost_volume(one: torch.Tensor, two: torch.Tensor) -> torch.Tensor:
 
 def backwarp(ten_input: torch.Tensor, ten_flow: torch.Tensor) -> torch.Tensor:
     b, _, h, w = ten_flow.shape
-    hor = torch.linspace(-1.0 + (1.0 / w), 1.0 - (1.0 / w), w).view(1, 1, 1, -1).repeat(1, 1, h, 1)
-    ver = torch.linspace(-1.0 + (1.0 / h), 1.0 - (1.0 / h), h).view(1, 1, -1, 1).repeat(1, 1, 1, w)
+    # (the grid in the flow's dtype: an fp64 call is fp64 throughout; in fp32 this is the reference's own default-dtype linspace)
+    hor = torch.linspace(-1.0 + (1.0 / w), 1.0 - (1.0 / w), w, dtype=ten_flow.dtype).view(1, 1, 1, -1).repeat(1, 1, h, 1)
+    ver = torch.linspace(-1.0 + (1.0 / h), 1.0 - (1.0 / h), h, dtype=ten_flow.dtype).view(1, 1, -1, 1).repeat(1, 1, 1, w)
     grid = torch.cat([hor, ver], 1)
     flow = torch.cat([ten_flow[:, 0:1] / ((ten_input.shape[3] - 1.0) / 2.0),
                       ten_flow[:, 1:2] / ((ten_input.shape[2] - 1.0) / 2.0)], 1)

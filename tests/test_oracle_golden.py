@@ -458,3 +458,31 @@ def test_pwc_cost_volume_hand_derived_known_answers():
         np.testing.assert_allclose(k, top, rtol=0, atol=1e-5 * max(1.0, float(np.abs(top).max())), err_msg=n + " (corr_oracle.c)")
         if n.startswith("A_") and "outside" not in n:
             assert np.count_nonzero(a) == 1 and np.count_nonzero(k) == 1, n
+
+
+def test_pwc_backwarp_oracle_runs_in_the_dtype_of_its_flow():
+    """pwc_ref.backwarp builds its grid in the flow's dtype.  fp32: bit-identical to the reference's wording (linspace in the
+    default dtype, ff_pwcnet.py:27-47).  fp64: fp64 throughout - with a zero flow the sample positions are the pixel centres
+    to fp64 rounding (an fp32-rounded grid misses them by 1e-8 of a pixel)."""
+    import torch.nn.functional as F
+    from oracle import pwc_ref
+
+    def worded(ten_input, ten_flow):
+        b, _, h, w = ten_flow.shape
+        hor = torch.linspace(-1.0 + (1.0 / w), 1.0 - (1.0 / w), w).view(1, 1, 1, -1).repeat(1, 1, h, 1)
+        ver = torch.linspace(-1.0 + (1.0 / h), 1.0 - (1.0 / h), h).view(1, 1, -1, 1).repeat(1, 1, 1, w)
+        flow = torch.cat([ten_flow[:, 0:1] / ((w - 1.0) / 2.0), ten_flow[:, 1:2] / ((h - 1.0) / 2.0)], 1)
+        out = F.grid_sample(torch.cat([ten_input, ten_flow.new_ones(b, 1, h, w)], 1), (torch.cat([hor, ver], 1) + flow).permute(0, 2, 3, 1),
+                            mode="bilinear", padding_mode="zeros", align_corners=False)
+        return out[:, :-1] * (out[:, -1:] > 0.999).to(out.dtype)
+
+    g = torch.Generator().manual_seed(27)
+    x, fl = torch.randn(2, 8, 17, 23, generator=g), torch.randn(2, 2, 17, 23, generator=g) * 3
+    got = pwc_ref.backwarp(x, fl)
+    assert got.dtype == torch.float32 and torch.equal(got, worded(x, fl)), "the fp32 oracle moved"
+    assert 0.2 < float((got != 0).any(1).float().mean()) < 0.95
+    got64 = pwc_ref.backwarp(x.double(), fl.double())
+    assert got64.dtype == torch.float64
+    still = pwc_ref.backwarp(x.double(), torch.zeros_like(fl).double())
+    assert float((still - x.double()).abs().max()) < 1e-12
+    assert float((worded(x.double(), torch.zeros_like(fl).double()) - x.double()).abs().max()) > 1e-10
