@@ -36,34 +36,41 @@ class PackedConv:
     Packed rows are [Cout][KH][KW][cin_pad]; re-packed by ff_pack_conv_weight
     whenever a source parameter changes (version counter) or moves.
     """
-    # defaults for subclasses that build their own state (pwcnet._TrainPacked)
-    cin_slices = None
-    use_bias = True
-    _w_raw = _wd_raw = _w_split = _wd_split = None
-    _used_f = _used_d = False      # get() / get_dgrad() have been asked for: prepack() keeps these layouts fresh
-    _gen = 0
-    _frag = _frag_of = None
-    _dfrag = _dfrag_of = None
 
-    force_f32 = False
-
-    def __init__(self, convs: Sequence[nn.Conv2d], cin_pad: Optional[int] = None,
-                 cin_slices: Optional[Sequence[Tuple[int, int]]] = None, use_bias: bool = True, force_f32: bool = False):
+    def __init__(self, convs: Sequence[nn.Module], cin_pad: Optional[int] = None,
+                 cin_slices: Optional[Sequence[Tuple[int, int]]] = None, use_bias: bool = True, force_f32: bool = False,
+                 pieces: Optional[Sequence[Tuple[int, int]]] = None, transposed: bool = False):
         """cin_slices: take only these input-channel ranges of the weights, in this order (a convolution is linear
         in its input channels: the GRU splits off the part that meets the loop-invariant context features);
         use_bias=False leaves the bias to the other part (and its gradient: params() then
-        holds None in the bias position)."""
+        holds None in the bias position).
+        pieces = [(real, padded), ...]: the input is a padded-piece tensor (FF-PWC's DenseNet buffers) - the weight's input
+        channels are scattered to their padded positions, zero columns at the pads.
+        transposed: the one member is an nn.ConvTranspose2d, run as the stride-1 convolution over the zero-dilated input
+        with the flipped, transposed kernel and pad k - 1 - padding."""
         self.convs = list(convs)
         c0 = self.convs[0]
         self.kh, self.kw = c0.kernel_size
-        self.stride = c0.stride[0]
-        self.pad = tuple(c0.padding)
+        self.transposed = transposed
+        self.stride = 1 if transposed else c0.stride[0]
+        self.pad = (self.kh - 1 - c0.padding[0], self.kw - 1 - c0.padding[1]) if transposed else tuple(c0.padding)
         self.dil = c0.dilation[0]
         self.cin_slices = list(cin_slices) if cin_slices is not None else None
         self.use_bias = use_bias
         self.force_f32 = force_f32      # exact-fp32 rows whatever the global conv precision (the range guard's repair route)
         self.cin = c0.in_channels if cin_slices is None else sum(hi - lo for lo, hi in cin_slices)
         self.cin_pad = cin_pad if cin_pad is not None else (self.cin + 3) // 4 * 4
+        self._idx = None                # pieces: position of every real input channel among the padded ones
+        if pieces is not None or transposed:
+            assert len(self.convs) == 1 and cin_slices is None and cin_pad is None and (not transposed or c0.dilation[0] == 1)
+            pieces = pieces if pieces is not None else [(self.cin, self.cin_pad)]
+            assert sum(r for r, _ in pieces) == c0.in_channels
+            idx, pos = [], 0
+            for real, padded in pieces:
+                idx += range(pos, pos + real)
+                pos += padded
+            self._idx = torch.tensor(idx, dtype=torch.long)
+            self.cin = self.cin_pad = pos
         self.cout = sum(c.out_channels for c in self.convs)
         for c in self.convs:
             assert c.kernel_size == c0.kernel_size and c.in_channels == c0.in_channels and c.stride == c0.stride
@@ -74,9 +81,17 @@ class PackedConv:
         self._dkey = None
         self.wd = None
         self._w_raw = self._wd_raw = self._w_split = self._wd_split = None
+        self._used_f = self._used_d = False      # get() / get_dgrad() have been asked for: prepack() keeps these layouts fresh
+        self._frag = self._frag_of = self._dfrag = self._dfrag_of = None
         _serial[0] += 1
         self._serial = _serial[0]
         _ALL_PACKED.add(self)
+
+    @property
+    def plain(self) -> bool:
+        """No pieces, not transposed: the packed rows are the members' own OIHW weights (channel slices at most), which is
+        what an FFPackJob (prepack) and ff_unpack_wgrad_group (fn.unpack_group) can express."""
+        return self._idx is None
 
     def _fwd_key(self):
         # (parameters through the module's own table: nn.Module.__getattr__ is several times slower, and a one-pair
@@ -101,6 +116,19 @@ class PackedConv:
         # (conv_small.hip) instead of wasting a 64-wide matrix tile on them
         return self.cout <= 2 and (self.kh, self.kw, self.stride) == (3, 3, 1) and self.pad == (1, 1)
 
+    def _oihw(self, c):
+        """Member c's weight as the kernels see it: [Cout_c][cin][KH][KW] (load-time plumbing)."""
+        wt = c.weight.detach()
+        if self.cin_slices is not None:
+            return torch.cat([wt[:, lo:hi] for lo, hi in self.cin_slices], 1).contiguous()
+        if self._idx is None:
+            return wt
+        if self.transposed:   # ConvTranspose2d [Cin][Cout][k][k] -> forward conv [Cout][Cin][k][k], flipped
+            wt = wt.permute(1, 0, 2, 3).flip(2, 3)
+        wp = torch.zeros((self.cout, self.cin_pad, self.kh, self.kw), dtype=torch.float32, device=wt.device)
+        wp[:, self._idx.to(wt.device)] = wt
+        return wp
+
     def get(self):
         self._used_f = True
         key = self._fwd_key()
@@ -112,10 +140,7 @@ class PackedConv:
             self.w = self._w_raw
             off = 0
             for c in self.convs:
-                wt = c.weight.detach()
-                if self.cin_slices is not None:
-                    wt = torch.cat([wt[:, lo:hi] for lo, hi in self.cin_slices], 1).contiguous()
-                ops.pack_conv_weight(wt, self.w, self.cin_pad, off)
+                ops.pack_conv_weight(self._oihw(c), self.w, self.cin_pad, off)
                 if c.bias is not None and self.use_bias:
                     self.b[off:off + c.out_channels].copy_(c.bias.detach())  # device memcpy
                 off += c.out_channels
@@ -125,6 +150,13 @@ class PackedConv:
             self._key = key
             self._gen += 1
         return self.w, self.b
+
+    def rows_f32(self):
+        """The forward rows in fp32 whatever the conv format (ops.deconv4x4s2_small reads them): the buffer get() packs
+        into before it splits.  Transposed layers only - prepack() never writes theirs, so it is always current."""
+        assert self.transposed
+        self.get()
+        return self._w_raw
 
     def get_dgrad(self):
         """Weights of the input-gradient convolution: [cin_pad][KH][KW][cout_pad], flipped + transposed, in the
@@ -140,10 +172,7 @@ class PackedConv:
             self.wd = self._wd_raw
             off = 0
             for c in self.convs:
-                wt = c.weight.detach()
-                if self.cin_slices is not None:
-                    wt = torch.cat([wt[:, lo:hi] for lo, hi in self.cin_slices], 1).contiguous()
-                ops.pack_conv_weight_dgrad(wt, self.wd, cout_pad, off)
+                ops.pack_conv_weight_dgrad(self._oihw(c), self.wd, cout_pad, off)
                 off += c.out_channels
             self.dfmt = ops.w_format()
             if self.dfmt != 0:
@@ -154,7 +183,7 @@ class PackedConv:
     def frag(self):
         """The forward rows in MFMA-fragment order (ops.pack_frag16) for the split-pair kernel; re-made per repack."""
         w, _ = self.get()
-        key = (self._gen, self._key, w.data_ptr())      # (_key carries the parameters' versions: subclasses that repack into a fresh buffer never bump _gen)
+        key = (self._gen, w.data_ptr())
         if self._frag_of != key:
             self._frag, self._frag_of = ops.pack_frag16(w, self.cout), key
         return self._frag
@@ -179,6 +208,8 @@ class PackedConv:
         return self._dfrag
 
     def __call__(self, xs, act=ACT_NONE, **kw):
+        """The forward launch: act(conv(cat(xs)) + bias); every other keyword (out, res, act_res, out_scale, want_stats,
+        the epilogues) goes to ops.conv2d as it is."""
         w, b = self.get()
         if not isinstance(xs, (list, tuple)):
             xs = [xs]
@@ -187,14 +218,41 @@ class PackedConv:
         return ops.conv2d(xs, w, b, self.cout, self.kh, self.kw, self.stride, self.pad, act=act, w_fmt=self.fmt,
                           dilation=self.dil, **kw)
 
+    def dgrad(self, g, amax, out=None, res=None):
+        """Input gradient over the cin_pad (concatenated) input channels for the output gradient g at stride 1 (a stride-2
+        caller zero-dilates g first): a forward convolution over g with the flipped rows.  amax: the word with max|g|;
+        res: added in the epilogue."""
+        wd, dfmt = self.get_dgrad()
+        d = self.dil
+        return ops.conv2d([g], wd, None, self.cin_pad, self.kh, self.kw, 1, (d * (self.kh - 1) - self.pad[0], d * (self.kw - 1) - self.pad[1]),
+                          w_fmt=dfmt, x_amax=amax if dfmt else None, dilation=d, out=out, res=res, w_frag=self.frag_dgrad())
+
+    def wgrad_acc(self, zeros, device):
+        """A zeroed (dw [cout][K], db [cout]) pair for wgrad() to add into, carved from ONE buffer of the allocator `zeros`
+        (torch.zeros, or a GraphScope's zeros)."""
+        n = self.cout * self.kh * self.kw * self.cin_pad
+        z = zeros((n + self.cout,), dtype=torch.float32, device=device)
+        return z[:n].view(self.cout, -1), z[n:]
+
+    def wgrad(self, xs, g, amax, acc=None):
+        """Packed weight-gradient rows + bias gradient of the output gradient g over the inputs xs, added into the pair
+        `acc` (wgrad_acc) or returned in fresh tensors: -> (dw, db)."""
+        dw, db = acc if acc is not None else (None, None)
+        return ops.conv2d_wgrad(xs, g, self.cout, self.kh, self.kw, self.stride, self.pad, g_amax=amax, want_db=True, dw=dw, db=db,
+                                dilation=self.dil)
+
     def params(self):
         """Parameter tensors in the order ConvFn receives (and returns gradients for) them."""
         return [t for cv in self.convs for t in (cv.weight, cv.bias if self.use_bias else None)]
 
     def unpack_wgrad(self, dwp, j, off):
-        """Packed weight gradient rows [off, off + Cout_j) -> gradient of convs[j].weight (zero outside cin_slices)."""
+        """Packed weight gradient rows [off, off + Cout_j) -> gradient of convs[j].weight, in the parameter's own shape
+        (zero outside cin_slices; the real channels of a pieced input; [Cin][Cout][k][k] for a transposed member)."""
         cv = self.convs[j]
         part = ops.unpack_conv_wgrad(dwp, cv.out_channels, self.cin, self.kh, self.kw, self.cin_pad, off)
+        if self._idx is not None:
+            part = part[:, self._idx.to(part.device)]
+            return part.flip(2, 3).permute(1, 0, 2, 3).contiguous() if self.transposed else part.contiguous()
         if self.cin_slices is None:
             return part
         full = torch.zeros_like(cv.weight)
@@ -270,7 +328,7 @@ def prepack(owner: nn.Module, device) -> int:
     # alive (bench.py's parity legs) otherwise pays for scanning and sorting all of theirs on every training step
     mine = owner.__dict__.get("_ff_packed_mine")
     if mine is None or mine[0] != (ids[0], _serial[0]):
-        found = sorted((pc for pc in _ALL_PACKED if type(pc) is PackedConv and id(pc.convs[0].weight) in ids[1]),
+        found = sorted((pc for pc in _ALL_PACKED if pc.plain and id(pc.convs[0].weight) in ids[1]),
                        key=lambda pc: pc._serial)
         mine = owner.__dict__["_ff_packed_mine"] = ((ids[0], _serial[0]), [weakref.ref(pc) for pc in found])
     todo = []
@@ -342,14 +400,13 @@ def invalidate_packed(module: nn.Module) -> int:
     write through `.data` (EMA weight swaps, `weight.data.clamp_()`, legacy optimisers) does not change - call this
     after such an update.  `load_state_dict` and `train()` / `eval()` of the top-level modules call it themselves.
     Returns the number of caches dropped."""
+    ids = {id(p) for p in module.parameters()}
     n = 0
+    for pc in list(_ALL_PACKED):       # found the way prepack() finds them: by the parameter they pack
+        if id(pc.convs[0]._parameters["weight"]) in ids:
+            pc._key = pc._dkey = None
+            n += 1
     for m in module.modules():
-        for v in vars(m).values():
-            vs = v if isinstance(v, (list, tuple)) else (v,)
-            for pc in vs:
-                if isinstance(pc, PackedConv):
-                    pc._key = pc._dkey = None
-                    n += 1
         if hasattr(m, "_ff_fold"):
             del m._ff_fold
             n += 1

@@ -149,7 +149,8 @@ class ParamGate(torch.autograd.Function):
 
 
 def _group_unpackable(pc) -> bool:
-    return _UNPACK_GROUP and type(pc).__name__ == "PackedConv" and len(pc.convs) <= 4 and len(pc.cin_slices or ()) <= 4
+    # (a group object other than a PackedConv - anything with convs and unpack_wgrad - is un-packed per member)
+    return _UNPACK_GROUP and getattr(pc, "plain", False) and len(pc.convs) <= 4 and len(pc.cin_slices or ()) <= 4
 
 
 def unpack_group(pc, dw: Tensor, db: Tensor) -> List[Optional[Tensor]]:
@@ -221,7 +222,6 @@ class ConvFn(torch.autograd.Function):
         ctx.take_res = (xs[0].data_ptr(), xs[0].numel()) if take_res else None
         res = tensors[nseg] if has_res else None
         assert not (has_res and act != ACT_NONE and out_scale != 1.0), "residual + activation + out_scale: no such layer"
-        w, b = pc.get()
         out = None
         if pad_out:  # allocate the channel-padded tensor; the caller owns channels >= Cout (filled by fill_tail)
             bsz, h, wd, _ = xs[0].shape
@@ -229,9 +229,8 @@ class ConvFn(torch.autograd.Function):
             wo = (wd + 2 * pc.pad[1] - pc.kw) // pc.stride + 1
             full = ops.empty_nhwc(bsz, ho, wo, (pc.cout + 3) // 4 * 4, xs[0])
             out = full[..., :pc.cout]
-        y = ops.conv2d(xs, w, b, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, act=ACT_NONE if has_res else act, out=out, res=res,
-                       act_res=act if has_res else ACT_NONE, out_scale=out_scale, w_fmt=pc.fmt, dilation=pc.dil,
-                       want_stats=stats_out is not None, w_frag=pc.frag() if pc.dma_f32_ok(xs) else None)
+        y = pc(xs, act=ACT_NONE if has_res else act, out=out, res=res, act_res=act if has_res else ACT_NONE, out_scale=out_scale,
+               want_stats=stats_out is not None)
         if stats_out is not None:      # per-sample {sum, sum of squares} of y for the InstanceNorm that follows (a constant
             y, st = y                  # of the graph: NormFn's backward differentiates through the statistics itself)
             stats_out.append(st)
@@ -265,18 +264,13 @@ class ConvFn(torch.autograd.Function):
         dxs = [None] * nseg
         skip = ctx.hints.res_grads.pop(ctx.take_res, None) if (ctx.take_res is not None and ctx.hints is not None) else None
         if need_dx:
-            wd, dfmt = pc.get_dgrad()
-            cin_tot = sum(x.shape[3] for x in xs)
             b, h, w, _ = xs[0].shape
             gi = g
             if pc.stride == 2:
                 gi = ops.dilate2(g, h + 2 * pc.pad[0] - pc.kh + 1, w + 2 * pc.pad[1] - pc.kw + 1)
             elif pc.stride != 1:
                 raise NotImplementedError("stride > 2")
-            d = pc.dil
-            dx = ops.conv2d([gi], wd, None, cin_tot, pc.kh, pc.kw, 1, (d * (pc.kh - 1) - pc.pad[0], d * (pc.kw - 1) - pc.pad[1]),
-                            w_fmt=dfmt, x_amax=amax if dfmt else None, dilation=d, w_frag=pc.frag_dgrad() if pc.stride == 1 else None,
-                            res=skip)          # (+ the skip connection's gradient: the block input's total leaves this launch)
+            dx = pc.dgrad(gi, amax, res=skip)      # (+ the skip connection's gradient: the block input's total leaves this launch)
             off = 0
             for i, x in enumerate(xs):
                 if ctx.needs_input_grad[NFIX + i]:
@@ -292,14 +286,11 @@ class ConvFn(torch.autograd.Function):
         if need_w and scope is not None:   # shared weights: add into the conv's buffer, deliver with the last application
             acc = scope.acc.get(pc)
             if acc is None:
-                kdim = pc.kh * pc.kw * sum(x.shape[3] for x in xs)
-                z = scope.zeros((pc.cout * kdim + pc.cout,), torch.float32, g.device)
-                acc = scope.acc[pc] = (z[:pc.cout * kdim].view(pc.cout, kdim), z[pc.cout * kdim:])
-            ops.conv2d_wgrad(xs, g, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, g_amax=amax, want_db=True, dw=acc[0], db=acc[1],
-                             dilation=pc.dil)
+                acc = scope.acc[pc] = pc.wgrad_acc(scope.zeros, g.device)
+            pc.wgrad(xs, g, amax, acc)
             return tuple(grads + [None] * ctx.nparam)      # the pass's ParamGate delivers the total
         elif need_w:   # weight + bias gradient in one launch (f16 matrix pipe unless the conv precision is fp32)
-            dwp, db = ops.conv2d_wgrad(xs, g, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, g_amax=amax, want_db=True, dilation=pc.dil)
+            dwp, db = pc.wgrad(xs, g, amax)
         off = 0
         for j, cv in enumerate(pc.convs):
             co = cv.out_channels

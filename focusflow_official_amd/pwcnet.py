@@ -17,7 +17,6 @@ resized first and the flow is resized / rescaled back, as the reference does; BA
 needs no resize).  Training: when gradients are recorded every step goes through an autograd Function whose backward is HIP as well
 (conv / transposed conv / dilated conv gradients, cost volume, backwarp); torch.cat builds the DenseNet tensors.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -39,113 +38,19 @@ def _pad4(c):
 # every DenseNet input then has a multiple of 32 channels and takes the patch-stationary / block-uniform conv kernels
 # instead of the generic im2col loader (which was 65 % of the forward).  The autograd path keeps the 84 / 4 / 4 layout.
 VOLP, FLP = 96, 16
+LAYOUTS = {"infer": (VOLP, FLP), "train": (84, 4)}      # (volume, flow / feature piece) padded widths
+C_ONE = {6: 0, 5: 128, 4: 96, 3: 64, 2: 32}             # tenOne channels of a decoder level (level 6 has the volume alone)
+GROWN = [(c, c) for _, c in GROWTH]
+
+
+def _input_pieces(level, layout):
+    """(real, padded) pieces of decoder `level`'s own input [volume | tenOne | flow | upfeat] in `layout`; the refiner reads
+    level 2's behind the five grown pieces."""
+    volp, flp = LAYOUTS[layout]
+    return [(81, volp)] + ([(C_ONE[level], C_ONE[level]), (2, flp), (2, flp)] if level < 6 else [])
 
 
 _DIRECT_DECONV = True     # ff_deconv4x4s2_small for netUpflow / netUpfeat
-
-class _Packed:
-    """Packed weights of one conv whose input is a padded-piece buffer: `pieces` = [(real, padded), ...]."""
-
-    def __init__(self, conv, pieces, transposed=False):
-        self.conv, self.pieces, self.transposed = conv, pieces, transposed
-        self.key = None
-
-    def get(self):
-        cv = self.conv
-        key = (ops.conv_precision(), cv.weight._version, cv.weight.data_ptr(), cv.bias._version)
-        if key != self.key:
-            w = cv.weight.detach()
-            if self.transposed:   # ConvTranspose2d [Cin][Cout][k][k] -> equivalent forward conv [Cout][Cin][k][k], flipped
-                w = w.permute(1, 0, 2, 3).flip(2, 3).contiguous()
-            co, ci, kh, kw = w.shape
-            cpad = sum(p for _, p in self.pieces)
-            assert ci == sum(r for r, _ in self.pieces)
-            wp = torch.zeros((co, cpad, kh, kw), dtype=torch.float32, device=w.device)
-            src = dst = 0
-            for real, padded in self.pieces:       # scatter real channels to their padded positions (load-time plumbing)
-                wp[:, dst:dst + real] = w[:, src:src + real]
-                src, dst = src + real, dst + padded
-            packed = torch.empty((co, kh * kw * cpad), dtype=torch.float32, device=w.device)
-            ops.pack_conv_weight(wp, packed, cpad, 0)
-            self.fmt = 0 if (co <= 2 and kh == 3 and not self.transposed) else ops.w_format()   # small heads: conv_small.hip (fp32)
-            self.w32 = packed if (self.transposed and co <= 2 and kh == 4) else None           # -> ops.deconv4x4s2_small
-            self.w = ops.pack_split(packed) if self.fmt else packed
-            self.b = cv.bias.detach()
-            self.cout, self.k = co, kh
-            self.key = key
-        return self.w, self.b
-
-    def __call__(self, x, act=ACT_NONE, pad=1, dilation=1, stride=1, out=None, res=None):
-        w, b = self.get()
-        return ops.conv2d([x], w, b, self.cout, self.k, self.k, stride, pad, act=act, out=out, res=res, w_fmt=self.fmt,
-                          dilation=dilation)
-
-
-class _TrainPacked(PackedConv):
-    """PackedConv for the autograd path when the input is a padded-piece tensor (pieces = [(real, padded), ...]) and /
-    or the module is a ConvTranspose2d (run as a stride-1 conv over the zero-dilated input with the flipped,
-    transposed kernel).  The kernels see a "virtual" weight (Cout, sum(padded), k, k); gradients are mapped back."""
-
-    def __init__(self, conv, pieces, transposed=False):
-        self.convs = [conv]
-        self.transposed = transposed
-        w = conv.weight
-        self.cout = w.shape[1] if transposed else w.shape[0]
-        self.kh, self.kw = w.shape[2], w.shape[3]
-        self.stride = 1 if transposed else conv.stride[0]
-        self.pad = (self.kh - 1 - conv.padding[0], self.kw - 1 - conv.padding[1]) if transposed else tuple(conv.padding)
-        self.dil = 1 if transposed else conv.dilation[0]
-        self.cin = self.cin_pad = sum(p for _, p in pieces)
-        idx, pos = [], 0
-        for real, padded in pieces:
-            idx += list(range(pos, pos + real))
-            pos += padded
-        assert len(idx) == (w.shape[0] if transposed else w.shape[1])
-        self._idx = torch.tensor(idx, dtype=torch.long)
-        self._key = self._dkey = None
-        self.w = self.b = self.wd = None
-
-    def _virtual(self):
-        cv = self.convs[0]
-        w = cv.weight.detach()
-        if self.transposed:   # ConvTranspose2d [Cin][Cout][k][k] -> forward conv [Cout][Cin][k][k], flipped
-            w = w.permute(1, 0, 2, 3).flip(2, 3)
-        wp = torch.zeros((self.cout, self.cin_pad, self.kh, self.kw), dtype=torch.float32, device=w.device)
-        wp[:, self._idx.to(w.device)] = w
-        return wp
-
-    def get(self):
-        cv = self.convs[0]
-        key = (ops.conv_precision(), cv.weight._version, cv.weight.data_ptr(), cv.bias._version)
-        if key != self._key:
-            wp = self._virtual()
-            self.w = torch.empty((self.cout, self.kh * self.kw * self.cin_pad), dtype=torch.float32, device=wp.device)
-            ops.pack_conv_weight(wp, self.w, self.cin_pad, 0)
-            small = self.cout <= 2 and (self.kh, self.kw, self.stride, self.dil) == (3, 3, 1, 1) and self.pad == (1, 1)
-            self.fmt = 0 if small else ops.w_format()
-            if self.fmt:
-                self.w = ops.pack_split(self.w)
-            self.b = cv.bias.detach()
-            self._key = key
-        return self.w, self.b
-
-    def get_dgrad(self):
-        cv = self.convs[0]
-        key = (ops.conv_precision(), cv.weight._version, cv.weight.data_ptr())
-        if key != self._dkey:
-            cout_pad = (self.cout + 3) // 4 * 4
-            self.wd = torch.zeros((self.cin_pad, self.kh * self.kw * cout_pad), dtype=torch.float32, device=cv.weight.device)
-            ops.pack_conv_weight_dgrad(self._virtual().contiguous(), self.wd, cout_pad, 0)
-            self.dfmt = ops.w_format()
-            if self.dfmt:
-                self.wd = ops.pack_split(self.wd)
-            self._dkey = key
-        return self.wd, self.dfmt
-
-    def unpack_wgrad(self, dwp, j, off):
-        full = ops.unpack_conv_wgrad(dwp, self.cout, self.cin_pad, self.kh, self.kw, self.cin_pad, off)   # virtual layout
-        g = full[:, self._idx.to(full.device)]
-        return g.flip(2, 3).permute(1, 0, 2, 3).contiguous() if self.transposed else g.contiguous()
 
 
 class _Dilate2(torch.autograd.Function):
@@ -205,31 +110,18 @@ class Extractor(nn.Module):
             for prefix in ("", "mask_"):
                 st = _stage(cin, c)
                 setattr(self, prefix + name, st)
-                self._packs[prefix + name] = [_Packed(st[0], [(cin, _pad4(cin))]), _Packed(st[2], [(c, c)]), _Packed(st[4], [(c, c)])]
+                # (the first conv of every branch reads a 4-channel NHWC4 image: a zero column at the pad)
+                self._packs[prefix + name] = [PackedConv([st[0]], _pad4(cin)), PackedConv([st[2]]), PackedConv([st[4]])]
             setattr(self, f"fusion{lvl + 1}", FusionUnit(c, fusion_type, lvl < 5))
             cin = c
-        # autograd path: plain PackedConvs (the first conv of every branch reads a 4-channel NHWC4 image)
-        self._tpacks = {k: [PackedConv([getattr(self, k)[2 * i]], 4 if (i == 0 and k.endswith("netOne")) else None) for i in range(3)]
-                        for k in self._packs}
-
-    def run_train(self, x, mask):
-        feats = []
-        for lvl, name in enumerate(self.NAMES):
-            for pk in self._tpacks[name]:
-                x = fn.conv(pk, x, act=ACT_LEAKY)
-            for pk in self._tpacks["mask_" + name]:
-                mask = fn.conv(pk, mask, act=ACT_LEAKY)
-            mask, x = getattr(self, f"fusion{lvl + 1}").run(mask, x)
-            feats.append(x)
-        return feats
 
     def run(self, x, mask):
         feats = []
         for lvl, name in enumerate(self.NAMES):
-            for i, pk in enumerate(self._packs[name]):
-                x = pk(x, act=ACT_LEAKY, stride=2 if i == 0 else 1)
-            for i, pk in enumerate(self._packs["mask_" + name]):
-                mask = pk(mask, act=ACT_LEAKY, stride=2 if i == 0 else 1)
+            for pk in self._packs[name]:
+                x = fn.conv(pk, x, act=ACT_LEAKY)
+            for pk in self._packs["mask_" + name]:
+                mask = fn.conv(pk, mask, act=ACT_LEAKY)
             mask, x = getattr(self, f"fusion{lvl + 1}").run(mask, x)
             feats.append(x)
         return feats
@@ -239,35 +131,23 @@ class Decoder(nn.Module):
     def __init__(self, level):
         super().__init__()
         self.level = level
-        cur = {6: 81, 5: 81 + 128 + 4, 4: 81 + 96 + 4, 3: 81 + 64 + 4, 2: 81 + 32 + 4}
-        c_one = {6: 0, 5: 128, 4: 96, 3: 64, 2: 32}[level]
-        self.base = [(81, VOLP)] + ([(c_one, c_one), (2, FLP), (2, FLP)] if level < 6 else [])
-        base_t = [(81, 84)] + ([(c_one, c_one), (2, 4), (2, 4)] if level < 6 else [])       # autograd path
+        c = sum(r for r, _ in _input_pieces(level, "infer"))
         if level < 6:
-            prev_c1 = {5: 0, 4: 128, 3: 96, 2: 64}[level]     # tenOne channels of the PREVIOUS (coarser) level
             self.netUpflow = nn.ConvTranspose2d(2, 2, 4, 2, 1)
-            self.netUpfeat = nn.ConvTranspose2d(cur[level + 1] + 448, 2, 4, 2, 1)
-            prev_base = [(81, VOLP)] + ([(prev_c1, prev_c1), (2, FLP), (2, FLP)] if level + 1 < 6 else [])
-            prev_base_t = [(81, 84)] + ([(prev_c1, prev_c1), (2, 4), (2, 4)] if level + 1 < 6 else [])
-            self._upflow = _Packed(self.netUpflow, [(2, 4)], transposed=True)
-            self._upfeat = _Packed(self.netUpfeat, [(c, c) for _, c in GROWTH] + prev_base, transposed=True)
-        c = cur[level]
-        grown = []
-        self._convs = []
-        self._tconvs = []                          # autograd path: the 84 / 4 / 4 padded-piece layout, through ConvFn
+            self.netUpfeat = nn.ConvTranspose2d(448 + sum(r for r, _ in _input_pieces(level + 1, "infer")), 2, 4, 2, 1)
+            self._upflow = PackedConv([self.netUpflow], pieces=[(2, 4)], transposed=True)      # the same in both layouts
+            self._upfeat = {lay: PackedConv([self.netUpfeat], pieces=GROWN + _input_pieces(level + 1, lay), transposed=True)
+                            for lay in LAYOUTS}
+        grown = 0
         for name, co in reversed(GROWTH):          # netOne first
-            conv = nn.Conv2d(c + sum(g for g, _ in grown), co, 3, 1, 1)
-            setattr(self, name, nn.Sequential(conv, nn.LeakyReLU(0.1)))
-            self._convs.append((name, _Packed(conv, grown + self.base)))
-            self._tconvs.append(_TrainPacked(conv, grown + base_t))
-            grown = [(co, co)] + grown
+            setattr(self, name, nn.Sequential(nn.Conv2d(c + grown, co, 3, 1, 1), nn.LeakyReLU(0.1)))
+            grown += co
         self.netSix = nn.Sequential(nn.Conv2d(c + 448, 2, 3, 1, 1))
-        self._six = _Packed(self.netSix[0], grown + self.base)
-        self.width = 448 + sum(p for _, p in self.base)
-        self._tsix = _TrainPacked(self.netSix[0], grown + base_t)
-        if level < 6:
-            self._tupflow = _TrainPacked(self.netUpflow, [(2, 4)], transposed=True)
-            self._tupfeat = _TrainPacked(self.netUpfeat, [(c, c) for _, c in GROWTH] + prev_base_t, transposed=True)
+        # per layout: the five DenseNet convs, netOne first (conv i reads the last i grown pieces in front of the input's), and netSix
+        self._convs = {lay: [PackedConv([getattr(self, name)[0]], pieces=GROWN[5 - i:] + _input_pieces(level, lay))
+                             for i, (name, _) in enumerate(reversed(GROWTH))] for lay in LAYOUTS}
+        self._six = {lay: PackedConv([self.netSix[0]], pieces=GROWN + _input_pieces(level, lay)) for lay in LAYOUTS}
+        self.width = 448 + sum(p for _, p in _input_pieces(level, "infer"))
 
     def run_train(self, one, two, prev):
         """Autograd twin of run(): torch.cat builds the DenseNet tensor (same padded-piece channel order)."""
@@ -275,14 +155,14 @@ class Decoder(nn.Module):
         if prev is None:
             feat = fn.ActFn.apply(_CostVolume84.apply(one, two), ACT_LEAKY)
         else:
-            flow = fn.conv(self._tupflow, _Dilate2.apply(prev["tenFlow"]), pad_out=True, fill_tail=zero_tail)
-            upfeat = fn.conv(self._tupfeat, _Dilate2.apply(prev["tenFeat"]), pad_out=True, fill_tail=zero_tail)
+            flow = fn.conv(self._upflow, _Dilate2.apply(prev["tenFlow"]), pad_out=True, fill_tail=zero_tail)
+            upfeat = fn.conv(self._upfeat["train"], _Dilate2.apply(prev["tenFeat"]), pad_out=True, fill_tail=zero_tail)
             warped = pwc.backwarp(two, flow, BACKWARP_SCALE[self.level])
             vol = fn.ActFn.apply(_CostVolume84.apply(one, warped), ACT_LEAKY)
             feat = torch.cat([vol, one, flow, upfeat], 3)
-        for pk in self._tconvs:
+        for pk in self._convs["train"]:
             feat = torch.cat([fn.conv(pk, feat, act=ACT_LEAKY), feat], 3)
-        return {"tenFlow": fn.conv(self._tsix, feat, pad_out=True, fill_tail=zero_tail), "tenFeat": feat}
+        return {"tenFlow": fn.conv(self._six["train"], feat, pad_out=True, fill_tail=zero_tail), "tenFeat": feat}
 
     def run(self, one, two, prev):
         """-> dict(tenFlow (B,h,w,4 padded), tenFeat = the level buffer)."""
@@ -295,23 +175,21 @@ class Decoder(nn.Module):
             feat_slot = buf[..., 448 + VOLP + one.shape[3] + FLP:]
             pf, pb = prev["tenFlow"], prev["tenFeat"]
             hp, wp = pf.shape[1], pf.shape[2]
-            if _DIRECT_DECONV:     # ConvTranspose2d(., 2, 4, 2, 1) without the zero-dilated copy and the matrix tile
-                for pk, src, slot in ((self._upflow, pf, flow_slot), (self._upfeat, pb, feat_slot)):
-                    pk.get()
-                    ops.deconv4x4s2_small(src, pk.w32, pk.b, 2, slot)
-            else:
-                self._upflow(ops.dilate2(pf, 2 * hp - 1, 2 * wp - 1), pad=2, out=flow_slot[..., :2])      # ConvTranspose2d
-                self._upfeat(ops.dilate2(pb, 2 * hp - 1, 2 * wp - 1), pad=2, out=feat_slot[..., :2])
+            for pk, src, slot in ((self._upflow, pf, flow_slot), (self._upfeat["infer"], pb, feat_slot)):
+                if _DIRECT_DECONV:     # ConvTranspose2d(., 2, 4, 2, 1) without the zero-dilated copy and the matrix tile
+                    ops.deconv4x4s2_small(src, pk.rows_f32(), pk.b, 2, slot)
+                else:
+                    pk(ops.dilate2(src, 2 * hp - 1, 2 * wp - 1), out=slot[..., :2])
             warped = pwc.backwarp(two, flow_slot, BACKWARP_SCALE[self.level])
             ops.act_copy(one, buf[..., 448 + VOLP: 448 + VOLP + one.shape[3]], ACT_NONE)
         vol = buf[..., 448:448 + VOLP]
         pwc._cv_fwd(one, warped, out=vol[..., :81], act=ACT_LEAKY)      # leaky_relu(volume) on the way out; the pad channels stay 0
         off = 448
-        for (name, pk), (_, co) in zip(self._convs, reversed(GROWTH)):
-            pk(buf[..., off:], act=ACT_LEAKY, out=buf[..., off - co:off])
-            off -= co
+        for pk in self._convs["infer"]:
+            pk(buf[..., off:], act=ACT_LEAKY, out=buf[..., off - pk.cout:off])
+            off -= pk.cout
         flow4 = torch.zeros((b, h, w, 4), dtype=torch.float32, device=one.device)   # 2 flow channels + 2 zero pads
-        self._six(buf, out=flow4[..., :2])
+        self._six["infer"](buf, out=flow4[..., :2])
         return {"tenFlow": flow4, "tenFeat": buf}
 
 
@@ -319,21 +197,18 @@ class Refiner(nn.Module):
     def __init__(self):
         super().__init__()
         chans = [(565, 128), (128, 128), (128, 128), (128, 96), (96, 64), (64, 32), (32, 2)]
-        self.dils = [1, 2, 4, 8, 16, 1, 1]
         layers = []
-        for i, ((ci, co), d) in enumerate(zip(chans, self.dils)):
+        for i, ((ci, co), d) in enumerate(zip(chans, [1, 2, 4, 8, 16, 1, 1])):
             layers.append(nn.Conv2d(ci, co, 3, 1, d, d))
             if i < 6:
                 layers.append(nn.LeakyReLU(0.1))
         self.netMain = nn.Sequential(*layers)
-        first = [(c, c) for _, c in GROWTH] + [(81, VOLP), (32, 32), (2, FLP), (2, FLP)]
-        first_t = [(c, c) for _, c in GROWTH] + [(81, 84), (32, 32), (2, 4), (2, 4)]
-        self._packs = [_Packed(self.netMain[0], first)] + [_Packed(self.netMain[2 * i], [(chans[i][0], chans[i][0])]) for i in range(1, 7)]
-        self._tpacks = [_TrainPacked(self.netMain[0], first_t)] + [PackedConv([self.netMain[2 * i]]) for i in range(1, 7)]
+        rest = [PackedConv([self.netMain[2 * i]]) for i in range(1, 7)]
+        self._packs = {lay: [PackedConv([self.netMain[0]], pieces=GROWN + _input_pieces(2, lay))] + rest for lay in LAYOUTS}
 
     def run_train(self, feat, flow):
         x = feat
-        for i, pk in enumerate(self._tpacks):
+        for i, pk in enumerate(self._packs["train"]):
             if i < 6:
                 x = fn.conv(pk, x, act=ACT_LEAKY)
             else:   # tenFlow + netRefiner(tenFeat), ff_pwcnet.py:424: the residual add rides in the conv epilogue
@@ -341,12 +216,12 @@ class Refiner(nn.Module):
 
     def run(self, feat, flow):
         x = feat
-        for i, (pk, d) in enumerate(zip(self._packs, self.dils)):
+        for i, pk in enumerate(self._packs["infer"]):
             if i < 6:
-                x = pk(x, act=ACT_LEAKY, pad=d, dilation=d)
+                x = pk(x, act=ACT_LEAKY)
             else:
                 out4 = torch.zeros_like(flow)
-                pk(x, pad=d, dilation=d, res=flow[..., :2], out=out4[..., :2])   # tenFlow + netRefiner(tenFeat), ff_pwcnet.py:424
+                pk(x, res=flow[..., :2], out=out4[..., :2])   # tenFlow + netRefiner(tenFeat), ff_pwcnet.py:424
                 return out4
 
 
@@ -445,8 +320,8 @@ class FF_PWCNET(nn.Module):
         if train:   # every step through an autograd Function (fn.GraphScope shares the extractor's weight gradients)
             fn.begin_graph(i1.device)
             try:
-                f1 = self.netExtractor.run_train(i1, m1)
-                f2 = self.netExtractor.run_train(i2, m2)
+                f1 = self.netExtractor.run(i1, m1)
+                f2 = self.netExtractor.run(i2, m2)
                 for level, dec in decoders:
                     est = dec.run_train(f1[level - 1], f2[level - 1], est)
                     if level == 2:

@@ -128,20 +128,9 @@ def eligible(ub, corr_fn, net, gru_pre) -> bool:
 
 
 def _fwd(pc, xs, out, act=ACT_NONE, res=None, out_scale=1.0):
-    w, b = pc.get()
-    if not isinstance(xs, (list, tuple)):
-        xs = [xs]
-    return ops.conv2d(xs, w, b, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, act=ACT_NONE if res is not None else act, out=out, res=res,
-                      act_res=act if res is not None else ACT_NONE, out_scale=out_scale, w_fmt=pc.fmt, dilation=pc.dil,
-                      w_frag=pc.frag() if pc.dma_f32_ok(xs) else None)
-
-
-def _dgrad(pc, g, amax, cin_tot, out, res=None):
-    """Input gradient of `pc` over its (concatenated) input channels: a forward convolution over g with the flipped rows."""
-    wd, dfmt = pc.get_dgrad()
-    d = pc.dil
-    return ops.conv2d([g], wd, None, cin_tot, pc.kh, pc.kw, 1, (d * (pc.kh - 1) - pc.pad[0], d * (pc.kw - 1) - pc.pad[1]),
-                      w_fmt=dfmt, x_amax=amax if dfmt else None, dilation=d, out=out, res=res, w_frag=pc.frag_dgrad())
+    """y = act(conv(cat(xs)) + bias [+ res]) * out_scale into `out`: with a residual the activation follows the sum."""
+    return pc(xs, act=ACT_NONE if res is not None else act, out=out, res=res, act_res=act if res is not None else ACT_NONE,
+              out_scale=out_scale)
 
 
 def _forward_fused(ub, corr_fn, coords1, T, net0, pre):
@@ -334,9 +323,7 @@ class UpdateLoopFn(torch.autograd.Function):
             if not want:
                 acc.append(None)
                 continue
-            kdim = pc.kh * pc.kw * sum(x.shape[3] for x in (xs if isinstance(xs, list) else [xs]))
-            z = torch.zeros(pc.cout * kdim + pc.cout, dtype=torch.float32, device=dev)
-            acc.append((z[:pc.cout * kdim].view(pc.cout, kdim), z[pc.cout * kdim:]))
+            acc.append(pc.wgrad_acc(torch.zeros, dev))
         main = torch.cuda.current_stream(dev)
         side = _side_stream(dev) if WGRAD_SIDE_STREAM else main
         pending_hi = T                      # iterations [t, pending_hi) have complete gradient stacks and no weight-gradient launch yet
@@ -355,8 +342,7 @@ class UpdateLoopFn(torch.autograd.Function):
                     if a_ is None:
                         continue
                     xs = xs if isinstance(xs, list) else [xs]
-                    ops.conv2d_wgrad([x[lo_t * b:hi_t * b] for x in xs], g[lo_t * b:hi_t * b], pc.cout, pc.kh, pc.kw, pc.stride, pc.pad,
-                                     g_amax=wmax[0, wi:wi + 1], want_db=True, dw=a_[0], db=a_[1], dilation=pc.dil)
+                    pc.wgrad([x[lo_t * b:hi_t * b] for x in xs], g[lo_t * b:hi_t * b], wmax[0, wi:wi + 1], a_)
 
         for t in range(T - 1, -1, -1):
             lo, hi = t * b, (t + 1) * b
@@ -367,10 +353,10 @@ class UpdateLoopFn(torch.autograd.Function):
                 _hip.call("ff_upsample_flow_bwd_ex", p(dout.contiguous()), p(S["flow4"][hi:hi + b]), 4, p(S["upmask"][lo:hi]), 576,
                           p(G["dflow"][lo:hi]), 4, p(G["mask"][lo:hi]), 0.25, p(wd(W_MASK)), b, h, w, st())
                 _hip.call("ff_act_bwd", p(G["dflow"][lo:hi]), 4, None, 0, p(G["dflow"][lo:hi]), 4, npix, 4, 4, ACT_NONE, 1.0, p(wd(W_FLOW)), st())
-                _dgrad(ub._mask2, G["mask"][lo:hi], wd(W_MASK), 256, dhid[..., 256:])
-                _dgrad(ub._flow2, G["dflow"][lo:hi], wd(W_FLOW), 256, dhid[..., :256])
+                ub._mask2.dgrad(G["mask"][lo:hi], wd(W_MASK), dhid[..., 256:])
+                ub._flow2.dgrad(G["dflow"][lo:hi], wd(W_FLOW), dhid[..., :256])
                 ops.act_bwd_into(dhid, S["hid"][lo:hi], ACT_RELU, G["hid"][lo:hi], wd(W_HID))
-                _dgrad(ub._heads, G["hid"][lo:hi], wd(W_HID), 128, dh, res=dh if dh_valid else None)
+                ub._heads.dgrad(G["hid"][lo:hi], wd(W_HID), dh, res=dh if dh_valid else None)
                 dh_valid = True
             if not dh_valid:
                 continue                                     # nothing reaches this iteration (its G slices are zero)
@@ -384,23 +370,23 @@ class UpdateLoopFn(torch.autograd.Function):
                 wz, wq = (W_ZR2, W_Q2) if k == 1 else (W_ZR1, W_Q1)
                 _hip.call("ff_gru_bwd_blend", p(dh), 128, p(later_zc), 256 if later_zc is not None else 0, p(dm) if later_zc is not None else None, 128,
                           p(zg), ops._ld(zg), p(q), 128, p(hprev), 128, p(gzr), 256, p(gq), 128, p(dh), 128, p(wd(wz)), p(wd(wq)), npix, 128, st())
-                _dgrad(gru._q_hm[k], gq, wd(wq), 256, dqc)                      # -> [d (r h) | d motion]
+                gru._q_hm[k].dgrad(gq, wd(wq), dqc)                      # -> [d (r h) | d motion]
                 _hip.call("ff_gru_bwd_rh", p(dqc), 256, p(rg), ops._ld(rg), p(hprev), 128, p(gzr[..., 128:]), 256, p(dh), 128, p(dm), 128,
                           1 if k == 1 else 0, p(wd(wz)), npix, 128, st())
-                _dgrad(gru._zr_hm[k], gzr, wd(wz), 256, dzc)                    # -> [d h | d motion]
+                gru._zr_hm[k].dgrad(gzr, wd(wz), dzc)                    # -> [d h | d motion]
                 later_zc = dzc
             _hip.call("ff_gru_bwd_out", p(dh), 128, p(dzc), 256, p(dm), 128, p(motion), 128, p(dh), 128, p(G["m"][lo:hi]), 128, 126, p(wd(W_M)),
                       npix, 128, st())
             # motion encoder (update.py:89-97), backwards
-            _dgrad(enc._cv, G["m"][lo:hi], wd(W_M), 256, d_c2f2)
+            enc._cv.dgrad(G["m"][lo:hi], wd(W_M), d_c2f2)
             gc2f2 = G["c2f2"][lo:hi]
             ops.act_bwd_into(d_c2f2[..., :192], S["c2f2"][lo:hi][..., :192], ACT_RELU, gc2f2[..., :192], wd(W_C2))
             ops.act_bwd_into(d_c2f2[..., 192:], S["c2f2"][lo:hi][..., 192:], ACT_RELU, gc2f2[..., 192:], wd(W_F2))
-            _dgrad(enc._c2, gc2f2[..., :192], wd(W_C2), 256, d_c1)
+            enc._c2.dgrad(gc2f2[..., :192], wd(W_C2), d_c1)
             ops.act_bwd_into(d_c1, S["c1"][lo:hi], ACT_RELU, G["c1"][lo:hi], wd(W_C1))
-            _dgrad(enc._c1p, G["c1"][lo:hi], wd(W_C1), 352, G["dcorr"][lo:hi])
+            enc._c1p.dgrad(G["c1"][lo:hi], wd(W_C1), G["dcorr"][lo:hi])
             if want_w[2]:        # convf1's input is the flow (no gradient): only its weights need d f1
-                _dgrad(enc._f2, gc2f2[..., 192:], wd(W_F2), 128, d_f1)
+                enc._f2.dgrad(gc2f2[..., 192:], wd(W_F2), d_f1)
                 ops.act_bwd_into(d_f1, S["f1"][lo:hi], ACT_RELU, G["f1"][lo:hi], wd(W_F1))
             if pending_hi - t >= WCHUNK or t == 0:
                 wgrad_slab(t, pending_hi)

@@ -608,6 +608,23 @@ def test_forward_variant_against_fp64(ops, c):
 
 
 @pytest.mark.gpu
+def test_fragment_order_weights_give_the_bits_of_row_order(ops):
+    """conv_dma.hip's fp32-input route reads the same split weights from rows or, given FFConvParams.w_frag, in
+    MFMA-fragment order (ops.pack_frag16): 128 -> 40 channels, 3x3, f16x3, at 1x9x17 (ragged against the 8-row tile and
+    the 16-column fragment, Cout off the N tile)."""
+    assert route([128], 40, 3, 3, 1, (1, 1), 1, 1, 9, 17, "f16x3").name.startswith("dma_f32")
+    g = torch.Generator().manual_seed(_seed("frag", 128, 40))
+    x = torch.randn(1, 9, 17, 128, generator=g).to(DEV)
+    wt, bias = torch.randn(40, 128, 3, 3, generator=g) / 34.0, torch.randn(40, generator=g).to(DEV)
+    wp = _packed(ops, wt, "f16x3")
+    rows = ops.conv2d([x], wp, bias, 40, 3, 3, 1, (1, 1), w_fmt=1, w_frag=None)
+    frag = ops.conv2d([x], wp, bias, 40, 3, 3, 1, (1, 1), w_fmt=1, w_frag=ops.pack_frag16(wp, 40))
+    assert torch.equal(rows, frag)
+    ref = F.conv2d(x.cpu().double().permute(0, 3, 1, 2), wt.double(), bias.cpu().double(), padding=1).permute(0, 2, 3, 1)
+    _check_values(rows.cpu(), ref, 2e-5 * max(1.0, float(ref.abs().max())), "dma_f32 from rows")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("norm,stats", MODES, ids=["stats", "norm", "norm+stats"])
 @pytest.mark.parametrize("mc", MODE_CASES, ids=lambda mc: mc.family.replace(" ", "_"))
 def test_normalise_on_load_and_epilogue_statistics(ops, mc, norm, stats):

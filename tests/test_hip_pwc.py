@@ -259,6 +259,33 @@ def test_ffpwcnet_training_step_gradients_match_oracle():
     assert all(p.grad is not None for p in m.parameters())
 
 
+def test_ffpwcnet_invalidate_packed_after_a_data_write():
+    """A write through `.data` leaves the version counters alone; after invalidate_packed() the next inference runs on the
+    new weights (every FF-PWC cache hangs in a dict or a list of lists: found through its parameter), bit for bit what a
+    fresh model loaded with the modified state dict computes."""
+    from argparse import Namespace
+    from focusflow_official_amd.pwcnet import FF_PWCNET
+    cfg = Namespace(TRAIN=Namespace(MASK_CHANNEL=3, MASK_MODAL="point"), MODEL=Namespace(FUSION="parallel", FUSION_TYPE="1x1conv"))
+    m = FF_PWCNET(cfg)
+    m.load_state_dict(_pwc_weights(), strict=True)
+    m = m.to(DEV).eval()
+    g = torch.Generator().manual_seed(8)
+    i1 = torch.nn.functional.interpolate(torch.rand(1, 3, 18, 18, generator=g), size=(64, 64), mode="bilinear", align_corners=False) * 255
+    i2 = torch.roll(i1, shifts=(1, -2), dims=(2, 3))
+    m1 = (torch.rand(1, 1, 64, 64, generator=g) < 0.02).float() * 255
+    args = [t.to(DEV) for t in (i1, i2, m1, torch.zeros_like(m1))]
+    with torch.no_grad():
+        first = m(*args)
+        m.netSix.netOne[0].weight.data.mul_(0.5)
+        assert m.invalidate_packed() > 0
+        second = m(*args)
+        fresh = FF_PWCNET(cfg)
+        fresh.load_state_dict({k: v.cpu() for k, v in m.state_dict().items()}, strict=True)
+        want = fresh.to(DEV).eval()(*args)
+    assert all(torch.equal(a, b) for a, b in zip(second, want))
+    assert not any(torch.equal(a, b) for a, b in zip(second, first))       # the coarsest decoder feeds every level
+
+
 @pytest.mark.parametrize("modal", ["frame", "neighborG", "neighborE", "context"])
 def test_ffpwcnet_mask_modes(modal):
     """FF-PWC's init_mask modes other than 'point' (ff_pwcnet.py:61-110), applied to the pre-processed (resized) inputs,

@@ -365,3 +365,24 @@ def test_invalidate_packed_drops_every_cache():
         pc._key = ("stale",)
     m.eval()
     assert all(pc._key is None for pc in pcs)
+
+
+def test_invalidate_packed_reaches_every_ffpwc_cache():
+    """FF-PWC keeps its PackedConvs in dicts and lists of lists; invalidate_packed finds them through their source
+    parameters (as prepack does), whatever holds them: every convolution weight of the model has at least one cache, and
+    invalidate_packed() / load_state_dict / eval() drop all of them."""
+    from argparse import Namespace
+    from focusflow_official_amd.cce import _ALL_PACKED
+    from focusflow_official_amd.pwcnet import FF_PWCNET
+    cfg = Namespace(TRAIN=Namespace(MASK_CHANNEL=3, MASK_MODAL="point"), MODEL=Namespace(FUSION="parallel", FUSION_TYPE="1x1conv"))
+    m = FF_PWCNET(cfg)
+    ids = {id(p) for p in m.parameters()}
+    pcs = [pc for pc in _ALL_PACKED if id(pc.convs[0].weight) in ids]
+    packed = {id(cv.weight) for pc in pcs for cv in pc.convs}
+    missing = [k for k, p in m.named_parameters() if p.dim() == 4 and id(p) not in packed]
+    assert not missing, missing
+    for drop in (m.invalidate_packed, lambda: m.load_state_dict(m.state_dict()), m.eval):
+        for pc in pcs:
+            pc._key = pc._dkey = ("stale",)
+        drop()
+        assert all(pc._key is None and pc._dkey is None for pc in pcs)
