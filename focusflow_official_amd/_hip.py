@@ -108,6 +108,9 @@ _SIGS = {
     "ff_coords_init": [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp],
     "ff_forward_interpolate": [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp],
     "ff_good_features": [_fp, C.c_int, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp, _fp, _fp, _fp, _fp],
+    "ff_frame_ingest": [_fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp],
+    "ff_pad_replicate": [_fp, C.c_int, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp],
+    "ff_keypoint_matches": [_fp, _fp, C.c_int, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],
@@ -209,7 +212,10 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for the hot path.")
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in _SIGS.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:      # (entry points are added without a new ABI version: a library from before one of them says so here)
+            raise FocusFlowHipError(f"{LIB_PATH} does not export {name}: it was built from older sources; "
+                                    "rebuild with `python -m focusflow_official_amd.build`")
         fn.argtypes = argtypes
         fn.restype = C.c_int
     lib.ff_last_error.restype = C.c_char_p

@@ -1,0 +1,240 @@
+"""Video sessions at the application's boundary: raw uint8 frames in, key-point matches out.
+
+`warm_start.FlowSequence` takes padded fp32 image pairs and returns the dense padded field.  A video application has
+neither: a decoder hands it one uint8 HWC frame at a time, whose height is usually no multiple of 8 (540, 1080), and a
+tracking or visual-odometry consumer wants the matches (x, y) -> (x + u, y + v) of the frame's key points.
+`FrameSequence` is the loop over frames (csrc/frame_io.hip does the conversions on the device):
+
+    seq = FrameSequence(model, raft_iters=12, keypoints=GoodFeatures())     # one per B videos that advance in lock-step
+    for frame in video:                      # uint8 (B,H,W,3) / (H,W,3): torch CPU (pinned or not), torch GPU, or numpy
+        res = seq.push(frame)                # None for the first frame of a sequence; afterwards flow(previous -> this)
+        res.flow_low, res.flow_up            # flow_up: the (B,2,H,W) unpadded view of the padded output (a slice)
+        res.matches, res.valid, res.count    # (B,N,4) fp32 [x, y, x + u, y + v], (B,N) uint8, (B) int32: the key points of
+                                             # the previous frame and where they went
+    seq.reset()                              # a sequence boundary: the next push returns None, the next pair starts cold
+"""
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import ops
+from .model import FF_RAFT_FUSION
+
+
+class FrameResult(NamedTuple):
+    flow_low: torch.Tensor
+    flow_up: torch.Tensor
+    matches: Optional[torch.Tensor]
+    valid: Optional[torch.Tensor]
+    count: Optional[torch.Tensor]
+
+
+class FrameSequence:
+    """`model(image1, image2, mask1, None, raft_iters, flow_init, test_mode=True)` over the consecutive frames of a video.
+
+    Every frame crosses the bus once, as uint8 (`copy_(frame, non_blocking=True)` into a static device buffer), and is
+    converted and replicate-padded once (ops.frame_ingest: what permute, float and utils.InputPadder(pad_mode).pad do, bit
+    for bit).  The session keeps two padded images, `image1` and `image2`.  Of the two ways to make this frame the next
+    pair's image1 - ping-pong buffers behind two captured graphs, or a copy - it takes the COPY: every step begins with one
+    device-to-device copy image1 <- image2 (and, with caller-supplied masks, mask1 <- the mask that came with that frame),
+    then ingests the new frame into image2.  One graph, and what the last pair read stays in place until the next push.
+
+    A step is: copy, ingest, detect, pad the mask, the model forward, forward_interpolate into the flow_init buffer
+    (warm_start=True), matches.  graph=True: one hipGraph replay; the first frame after construction, reset() or a change
+    of (B,H,W), mask dtype or device is only ingested, the graph is captured on the push after it, and such a change also
+    starts a new sequence.  The range guard works as in graph.GraphedForward: static guard words, ops.guard_check before a
+    replay, ops.guard_queue behind it.  graph=False: the same operations issued one by one.  push() adds no host
+    synchronisation of its own (a capture waits for the device, as every capture does).
+
+    keypoints=det (keypoints.GoodFeatures): det runs on the unpadded interior of image1, as the reference makes its masks
+    from the original image; the mask is then replicate-padded as evaluate.evaluate_loader pads masks, mask1 =
+    InputPadder.pad(det(frame)), and the points feed the matches.  Plain RAFT (use_fusion=None) reads no mask: there a
+    detector feeds the matches only and `mask1` is None.  FF-RAFT without a detector takes push(frame, mask=m), m (B,1,H,W)
+    or (B,H,W), uint8 or fp32, unpadded: it is padded on the device and read when this frame is image1; `matches`, `valid`
+    and `count` are then None.  mask2 is always None: init_mask overwrites it in every mode (ff_raft.py:23-72).
+
+    The tensors of a result are the session's static buffers: valid until the next push.  A frame in pinned host memory is
+    read by an asynchronous copy: leave it alone until work enqueued after the push has finished (the event a consumer
+    waits for anyway before it reads the matches)."""
+
+    def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel"):
+        if not isinstance(model, FF_RAFT_FUSION):
+            raise ValueError(f"model: FrameSequence drives FF_RAFT_FUSION, whose forward takes flow_init; {type(model).__name__} "
+                             "(FF_PWCNET has no flow_init) runs pair by pair through graph.GraphedForward")
+        if layout not in ("hwc", "chw"):
+            raise ValueError(f"layout={layout!r}: 'hwc' or 'chw'")
+        if order not in ("rgb", "bgr"):
+            raise ValueError(f"order={order!r}: 'rgb' or 'bgr'")
+        self.model, self.iters, self.warm_start, self.graph = model, raft_iters, bool(warm_start), bool(graph)
+        self.keypoints, self.layout, self.order, self.pad_mode = keypoints, layout, order, pad_mode
+        self._reads_mask = getattr(model, "mask_modal", None) is not None
+        self._require_eval()
+        self._key = None
+        self._drop()
+
+    def _require_eval(self):
+        if self.model.training:
+            raise ValueError("model: FrameSequence runs the eval-mode forward: call model.eval() first")
+
+    def _drop(self):
+        self._cuda_graph = self._result = self._guard_words = None      # (the old graph's buffers go before the new ones come)
+        self._u8 = self._mask_in = self._img1 = self._img2 = self._mask1 = self._mask_next = self._mask_det = self._flow_init = None
+        self._frames = 0      # frames of the running sequence that have been ingested
+
+    @property
+    def mask1(self):
+        """The padded (B,1,Hp,Wp) mask the last pair's forward read for its first frame; None before the first pair and
+        for plain RAFT."""
+        return self._mask1 if self._reads_mask and self._frames >= 2 else None
+
+    @property
+    def flow_init(self):
+        """What the next pair starts from: the session's (B,2,Hp/8,Wp/8) buffer (zeros: a cold start); None without
+        warm_start or before the first frame."""
+        return self._flow_init
+
+    def reset(self):
+        """A sequence boundary: the next push returns None and the pair after it starts cold."""
+        self._frames = 0
+        if self._flow_init is not None:
+            self._flow_init.zero_()
+
+    # ---- inputs -----------------------------------------------------------------------------------------------------
+    def _frame(self, frame):
+        if not isinstance(frame, torch.Tensor):
+            frame = torch.as_tensor(frame)
+        if frame.dtype != torch.uint8:
+            raise ValueError(f"frame: uint8 expected (the decoder's bytes), got {frame.dtype}; float images go to warm_start.FlowSequence")
+        if frame.dim() == 3:
+            frame = frame.unsqueeze(0)
+        if frame.dim() != 4:
+            raise ValueError(f"frame: (B,H,W,3) / (H,W,3) for layout 'hwc', (B,3,H,W) / (3,H,W) for 'chw', got {tuple(frame.shape)}")
+        c = frame.shape[3] if self.layout == "hwc" else frame.shape[1]
+        if c != 3:
+            raise ValueError(f"frame: {c} channels in layout {self.layout!r} (shape {tuple(frame.shape)}), 3 expected: "
+                             "pass frame[..., :3] of an RGBA frame")
+        return frame
+
+    def _mask(self, mask, b, h, w):
+        if self.keypoints is not None and self._reads_mask:
+            if mask is not None:
+                raise ValueError("mask: this session detects mask1 itself (keypoints=...): pass no mask")
+            return None
+        if not self._reads_mask:
+            if mask is not None:
+                raise ValueError("mask: plain RAFT (use_fusion=None) reads no mask")
+            return None
+        if mask is None:
+            raise ValueError("mask: this model reads a key-point mask of every frame: push(frame, mask=m), or give the session a detector (keypoints=...)")
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.as_tensor(mask)
+        if mask.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"mask: uint8 or float32 expected, got {mask.dtype}")
+        if mask.dim() == 4 and mask.shape[1] == 1:
+            mask = mask[:, 0]
+        if tuple(mask.shape) != (b, h, w):
+            raise ValueError(f"mask: ({b},1,{h},{w}) or ({b},{h},{w}) expected for this frame, got {tuple(mask.shape)}")
+        return mask
+
+    # ---- the step ---------------------------------------------------------------------------------------------------
+    def _allocate(self, frame, mask, device):
+        b, h, w = self._bhw
+        left, top, hp, wp = self._pad
+        f32 = dict(dtype=torch.float32, device=device)
+        self._u8 = torch.empty(tuple(frame.shape), dtype=torch.uint8, device=device)
+        self._img1, self._img2 = torch.zeros((b, 3, hp, wp), **f32), torch.zeros((b, 3, hp, wp), **f32)
+        if self._reads_mask:
+            self._mask1 = torch.zeros((b, 1, hp, wp), **f32)
+        if mask is not None:
+            self._mask_in = torch.empty((b, h, w), dtype=mask.dtype, device=device)
+            self._mask_next = torch.zeros((b, 1, hp, wp), **f32)
+        if self.keypoints is not None:
+            self._mask_det = torch.zeros((b, 1, h, w), **f32)
+        if self.warm_start:
+            self._flow_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
+
+    def _ingest(self):
+        """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
+        ops.frame_ingest(self._u8, self.layout, self.order, self.pad_mode, out=self._img2)
+        if self._mask_in is not None:
+            ops.pad_replicate(self._mask_in, self.pad_mode, out=self._mask_next)
+
+    def _step(self):
+        b, h, w = self._bhw
+        left, top, hp, wp = self._pad
+        self._img1.copy_(self._img2)
+        if self._mask_next is not None:
+            self._mask1.copy_(self._mask_next)
+        self._ingest()
+        det, points, count = self.keypoints, None, None
+        if det is not None:
+            inner = self._img1[:, :, top:top + h, left:left + w]      # (a dense innermost dimension: no copy)
+            _, points, count = ops.good_features(inner, det.max_corners, det.quality_level, det.min_distance, out=self._mask_det,
+                                                 return_points=True, ws=det._workspace(inner))
+            if self._reads_mask:
+                ops.pad_replicate(self._mask_det, self.pad_mode, out=self._mask1)
+        kw = dict(flow_init=self._flow_init) if self._flow_init is not None else {}
+        flow_low, flow_up = self.model(self._img1, self._img2, self._mask1, None, raft_iters=self.iters, test_mode=True, **kw)
+        if self.warm_start:
+            ops.forward_interpolate(flow_low, out=self._flow_init)
+        matches = valid = None
+        if det is not None:
+            matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
+        return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, count)
+
+    def _capture(self, warmup=3):
+        """graph.GraphedForward's capture around `_step`: warm-up steps on a side stream (they pack weights, set kernel
+        attributes, decide the routes and warm the allocator), what they changed put back, then the capture with static
+        guard words."""
+        keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init) if t is not None]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._step()
+            for t, saved in keep:
+                t.copy_(saved)
+        torch.cuda.current_stream().wait_stream(side)
+        ops.guard_check(sync=True)
+        self._guard_words = torch.zeros(2, dtype=torch.int32, device=self._img1.device) if ops.RANGE_GUARD else None
+        st = ops._guard_state()
+        st["capture_words"] = self._guard_words
+        self._cuda_graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(self._cuda_graph):
+                self._result = self._step()
+        finally:
+            st["capture_words"] = None
+
+    def push(self, frame, mask=None):
+        """The next frame of the video (and, for FF-RAFT without a detector, its unpadded key-point mask).  -> None for the
+        first frame of a sequence, afterwards a FrameResult for the pair (previous frame, this frame)."""
+        self._require_eval()
+        frame = self._frame(frame)
+        b, h, w = (frame.shape[0], frame.shape[1], frame.shape[2]) if self.layout == "hwc" else (frame.shape[0], frame.shape[2], frame.shape[3])
+        mask = self._mask(mask, b, h, w)
+        device = next(self.model.parameters()).device
+        if device.type != "cuda":
+            raise ops._hip.FocusFlowHipError("FrameSequence: the model must be on a HIP device; there is no CPU fallback")
+        key = (b, h, w, None if mask is None else mask.dtype, device)
+        with torch.no_grad(), torch.cuda.device(device):
+            if key != self._key:      # a new shape: new buffers, a new graph, a new sequence
+                self._drop()
+                self._key, self._bhw, self._pad = key, (b, h, w), ops.pad_offsets(h, w, self.pad_mode)
+                self._allocate(frame, mask, device)
+            self._u8.copy_(frame, non_blocking=True)
+            if mask is not None:
+                self._mask_in.copy_(mask, non_blocking=True)
+            self._frames += 1
+            if self._frames == 1:
+                self._ingest()
+                return None
+            if not self.graph:
+                return self._step()
+            if self._cuda_graph is None:
+                self._capture()
+            ops.guard_check()                   # (raises if an earlier replay left the split formats' range)
+            self._cuda_graph.replay()
+            if self._guard_words is not None:
+                ops.guard_queue(self._guard_words, "FrameSequence replay", getattr(self.model, "flow_net", None))
+            return self._result

@@ -1025,6 +1025,112 @@ def good_features(image: Tensor, max_corners: int = 500, quality_level: float = 
     return (out, points, count) if return_points else out
 
 
+def pad_offsets(h: int, w: int, pad_mode: str = "sintel"):
+    """(left, top, Hp, Wp) of utils.InputPadder((h, w), pad_mode): replicate padding to multiples of 8, centred for
+    'sintel', at the bottom (and centred horizontally) for anything else (KITTI)."""
+    pad_h, pad_w = (-h) % 8, (-w) % 8
+    return pad_w // 2, (pad_h // 2 if pad_mode == "sintel" else 0), h + pad_h, w + pad_w
+
+
+def _require_device(t: Tensor, name: str, what: str, dtypes):
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise _hip.FocusFlowHipError(f"{name}: {what} must be a tensor on a HIP device (got {'a CPU tensor' if isinstance(t, Tensor) else type(t).__name__}); "
+                                     "there is no CPU fallback")
+    if t.dtype not in dtypes:
+        raise _hip.FocusFlowHipError(f"{name}: {what} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+
+
+def _padded_out(name: str, out: Optional[Tensor], shape, device) -> Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    _require_device(out, name, "out", (torch.float32,))
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise _hip.FocusFlowHipError(f"{name}: out must be contiguous {tuple(shape)} on {device}, got {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    return out
+
+
+def frame_ingest(frame: Tensor, layout: str = "hwc", order: str = "rgb", pad_mode: str = "sintel", out: Optional[Tensor] = None) -> Tensor:
+    """A decoder's uint8 frame -> the fp32 (B,3,Hp,Wp) R,G,B tensor the models take (csrc/frame_io.hip): what
+    x.permute(0, 3, 1, 2).float() and utils.InputPadder(x.shape, pad_mode).pad do, bit for bit, in one launch.
+    frame: uint8 (B,H,W,3) / (H,W,3) for layout 'hwc', (B,3,H,W) / (3,H,W) for 'chw', any strides (a crop, the [..., :3]
+    view of an RGBA frame); order 'rgb' or 'bgr'; out: a contiguous fp32 (B,3,Hp,Wp) tensor (default: a new one).
+    Enqueues only, so it can be captured."""
+    _require_device(frame, "frame_ingest", "frame", (torch.uint8,))
+    if layout not in ("hwc", "chw"):
+        raise _hip.FocusFlowHipError(f"frame_ingest: layout = {layout!r} ('hwc' or 'chw')")
+    if order not in ("rgb", "bgr"):
+        raise _hip.FocusFlowHipError(f"frame_ingest: order = {order!r} ('rgb' or 'bgr')")
+    if frame.dim() == 3:
+        frame = frame.unsqueeze(0)
+    if frame.dim() != 4:
+        raise _hip.FocusFlowHipError(f"frame_ingest: frame must be (B,H,W,3) / (H,W,3) [hwc] or (B,3,H,W) / (3,H,W) [chw], got {tuple(frame.shape)}")
+    if layout == "hwc":
+        b, h, w, c = frame.shape
+        ld_b, ld_row, ld_col, ld_c = frame.stride()
+    else:
+        b, c, h, w = frame.shape
+        ld_b, ld_c, ld_row, ld_col = frame.stride()
+    if c != 3:
+        raise _hip.FocusFlowHipError(f"frame_ingest: frame has {c} channels in layout {layout!r}, shape {tuple(frame.shape)}: 3 expected "
+                                     "(take frame[..., :3] of an RGBA frame)")
+    left, top, hp, wp = pad_offsets(h, w, pad_mode)
+    out = _padded_out("frame_ingest", out, (b, 3, hp, wp), frame.device)
+    _hip.call("ff_frame_ingest", _p(frame), ld_b, ld_row, ld_col, ld_c, int(order == "bgr"), b, h, w, left, top, hp, wp, _p(out), _stream())
+    return out
+
+
+def pad_replicate(mask: Tensor, pad_mode: str = "sintel", out: Optional[Tensor] = None) -> Tensor:
+    """utils.InputPadder(mask.shape, pad_mode).pad for a one-channel mask, into fp32 (csrc/frame_io.hip): mask (B,1,H,W) or
+    (B,H,W), uint8 or fp32, any strides; out: a contiguous fp32 (B,1,Hp,Wp) tensor (default: a new one).  Bit-identical to
+    F.pad(mask.float(), mode='replicate').  Enqueues only, so it can be captured."""
+    _require_device(mask, "pad_replicate", "mask", (torch.uint8, torch.float32))
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() != 3:
+        raise _hip.FocusFlowHipError(f"pad_replicate: mask must be (B,1,H,W) or (B,H,W), got {tuple(mask.shape)}")
+    b, h, w = mask.shape
+    left, top, hp, wp = pad_offsets(h, w, pad_mode)
+    out = _padded_out("pad_replicate", out, (b, 1, hp, wp), mask.device)
+    _hip.call("ff_pad_replicate", _p(mask), int(mask.dtype == torch.uint8), mask.stride(0), mask.stride(1), mask.stride(2), b, h, w, left, top, hp, wp,
+              _p(out), _stream())
+    return out
+
+
+def keypoint_matches(points: Tensor, count: Tensor, flow_up: Tensor, left: int, top: int, h: int, w: int,
+                     out: Optional[Tensor] = None, valid: Optional[Tensor] = None):
+    """The flow at key points as matches (csrc/frame_io.hip).  points (B,N,2) int32 [x, y] and count (B) int32 as
+    good_features(return_points=True) gives them, in coordinates of the unpadded h x w frame; flow_up (B,2,Hp,Wp) fp32, any
+    strides, the padded field whose frame starts at (left, top).  -> (matches (B,N,4) fp32 [x, y, x + u, y + v], valid (B,N)
+    uint8: the target lies inside the frame); rows from count[b] on hold -1 and 0.  out / valid: contiguous tensors to
+    write into (default: new ones).  Enqueues only, so it can be captured."""
+    _require_device(points, "keypoint_matches", "points", (torch.int32,))
+    _require_device(count, "keypoint_matches", "count", (torch.int32,))
+    _require_device(flow_up, "keypoint_matches", "flow_up", (torch.float32,))
+    if points.dim() != 3 or points.shape[2] != 2 or not points.is_contiguous():
+        raise _hip.FocusFlowHipError(f"keypoint_matches: points must be contiguous (B,N,2), got {tuple(points.shape)} strides {points.stride()}")
+    b, n, _ = points.shape
+    if tuple(count.shape) != (b,) or not count.is_contiguous():
+        raise _hip.FocusFlowHipError(f"keypoint_matches: count must be contiguous ({b},), got {tuple(count.shape)}")
+    if flow_up.dim() != 4 or flow_up.shape[0] != b or flow_up.shape[1] != 2:
+        raise _hip.FocusFlowHipError(f"keypoint_matches: flow_up must be ({b},2,Hp,Wp), got {tuple(flow_up.shape)}")
+    hp, wp = flow_up.shape[2:]
+    if out is None:
+        out = torch.empty((b, n, 4), dtype=torch.float32, device=points.device)
+    else:
+        _require_device(out, "keypoint_matches", "out", (torch.float32,))
+        if tuple(out.shape) != (b, n, 4) or not out.is_contiguous():
+            raise _hip.FocusFlowHipError(f"keypoint_matches: out must be contiguous {(b, n, 4)}, got {tuple(out.shape)} strides {out.stride()}")
+    if valid is None:
+        valid = torch.empty((b, n), dtype=torch.uint8, device=points.device)
+    else:
+        _require_device(valid, "keypoint_matches", "valid", (torch.uint8,))
+        if tuple(valid.shape) != (b, n) or not valid.is_contiguous():
+            raise _hip.FocusFlowHipError(f"keypoint_matches: valid must be contiguous {(b, n)}, got {tuple(valid.shape)} strides {valid.stride()}")
+    _hip.call("ff_keypoint_matches", _p(points), _p(count), n, _p(flow_up), flow_up.stride(0), flow_up.stride(1), flow_up.stride(2), flow_up.stride(3),
+              b, int(left), int(top), int(h), int(w), hp, wp, _p(out), _p(valid), _stream())
+    return out, valid
+
+
 def coords_step(coords1: Tensor, delta: Optional[Tensor], flow4: Optional[Tensor], slot: Optional[Tensor]):
     b, h, w, _ = coords1.shape
     _hip.call("ff_coords_step", _p(coords1), _p(delta), _ld(delta) if delta is not None else 0, _p(flow4), _p(slot),

@@ -59,7 +59,11 @@ const char* ff_last_error(void);
  *   7 (round 5): entry points only: ff_gru_bwd_blend / _rh / _out, ff_sum_stack, ff_upsample_flow_bwd_ex (the recorded
  *                update loop's backward), ff_gru_pass_rec
  *   7 (unchanged): entry points only: ff_forward_interpolate / ff_forward_interpolate_ws (warm start of video inference)
- *   7 (unchanged): entry points only: ff_good_features / ff_good_features_ws (key-point masks on the device) */
+ *   7 (unchanged): entry points only: ff_good_features / ff_good_features_ws (key-point masks on the device)
+ *   7 (unchanged): entry points only: ff_frame_ingest, ff_pad_replicate, ff_keypoint_matches (video sessions: uint8 frames
+ *                in, key-point matches out).  No struct or argument list changed, so a caller built against an earlier 7 is
+ *                still right; a caller that needs these three finds out from the symbols (the Python binding names the
+ *                missing one and asks for a rebuild) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -388,6 +392,33 @@ int ff_good_features_ws(int B, int H, int W);
 int ff_good_features(const float* image, int channels, long long ld_b, long long ld_c, long long ld_row, int B, int H, int W,
                      int max_corners, double quality_level, int min_distance, void* ws, float* mask, int* points, int* count,
                      void* stream);
+/* A decoder's uint8 frame -> the fp32 (B,3,Hp,Wp) R,G,B tensor the models take, replicate-padded: replaces
+ * x.permute(0, 3, 1, 2).float() followed by InputPadder.pad (core/utils/utils.py:7-24, F.pad(mode="replicate")) of the
+ * reference's callers (evaluate.py).  Source element (b, y, x, c) is src[b ld_b + y ld_row + x ld_col + c ld_c] (strides in
+ * elements): HWC (ld_col = 3, ld_c = 1), CHW (ld_col = 1, ld_c = H W), a crop of a larger frame, the first three channels
+ * of an RGBA frame (ld_col = 4).  swap_rb = 1: the source is B,G,R.  dst is contiguous:
+ *   dst[b][c][y][x] = (float) src(b, clamp(y - top, 0, H-1), clamp(x - left, 0, W-1), swap_rb ? 2 - c : c)
+ * uint8 -> fp32 is exact: the result has the bits of the torch route.  Refused (FF_EINVAL): left or top < 0, left + W > Wp,
+ * top + H > Hp, swap_rb not 0 / 1.  Enqueues only (capturable): one launch. */
+int ff_frame_ingest(const unsigned char* src, long long ld_b, long long ld_row, long long ld_col, long long ld_c, int swap_rb, int B, int H,
+                    int W, int left, int top, int Hp, int Wp, float* dst, void* stream);
+/* The same replicate padding (F.pad(mode="replicate"), as evaluate.py pads its masks with InputPadder) for a one-channel
+ * plane: src_is_u8 = 1 a uint8 source, 0 an fp32 one; element (b, y, x) is src[b ld_b + y ld_row + x ld_col]; dst is the
+ * contiguous fp32 (B,1,Hp,Wp).  Values are copied (uint8: converted exactly).  Refusals as above.  One launch. */
+int ff_pad_replicate(const void* src, int src_is_u8, long long ld_b, long long ld_row, long long ld_col, int B, int H, int W, int left, int top,
+                     int Hp, int Wp, float* dst, void* stream);
+/* Key points and the flow at them -> matches: what a tracking consumer gathers from the dense field with torch indexing
+ * after InputPadder.unpad (utils.py:21-24).  points (B,N,2) int32 [x, y] and count (B) int32 as ff_good_features writes them,
+ * in coordinates of the unpadded H x W frame; flow_up element (b, c, y, x) is flow_up[b ld_b + c ld_c + y ld_row + x ld_col], a
+ * padded (B,2,Hp,Wp) field whose frame starts at (left, top).  For n < count[b] (count is read as given, rows from N on do
+ * not exist):
+ *   u = flow_up(b, 0, y + top, x + left), v = flow_up(b, 1, ...);  matches[b][n] = [x, y, x + u, y + v] (one fp32 add each)
+ *   valid[b][n] = 1 iff 0 <= x + u <= W - 1 and 0 <= y + v <= H - 1 (a NaN gives 0)
+ * Rows from count[b] on - and a row whose point lies outside the frame, which the flow is never read for - hold -1 in all
+ * four fields and valid = 0.  matches (B,N,4) fp32 contiguous and 16-byte aligned, valid (B,N) uint8 contiguous.  One launch. */
+int ff_keypoint_matches(const int* points, const int* count, int N, const float* flow_up, long long ld_b, long long ld_c, long long ld_row,
+                        long long ld_col, int B, int left, int top, int H, int W, int Hp, int Wp, float* matches, unsigned char* valid,
+                        void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
