@@ -111,6 +111,10 @@ _SIGS = {
     "ff_frame_ingest": [_fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp],
     "ff_pad_replicate": [_fp, C.c_int, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp],
     "ff_keypoint_matches": [_fp, _fp, C.c_int, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp],
+    "ff_tracks_replenish": [_fp, _fp, _fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp],
+    "ff_tracks_mask": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp],
+    "ff_tracks_advance": [_fp, _fp, _fp, C.c_int, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp,
+                          _fp, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],

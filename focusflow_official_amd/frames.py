@@ -12,21 +12,70 @@ tracking or visual-odometry consumer wants the matches (x, y) -> (x + u, y + v) 
         res.matches, res.valid, res.count    # (B,N,4) fp32 [x, y, x + u, y + v], (B,N) uint8, (B) int32: the key points of
                                              # the previous frame and where they went
     seq.reset()                              # a sequence boundary: the next push returns None, the next pair starts cold
+
+With tracks (tracks.TrackTable, csrc/tracks.hip) the session follows its key points over the frames and gives each a persistent id:
+
+    seq = FrameSequence(model, raft_iters=12, keypoints=GoodFeatures(), tracks=True)     # or tracks=N slots
+    res = seq.push(frame)
+    res.matches, res.valid                   # per SLOT: (B,N,4) [x, y, x', y'] at sub-pixel positions, (B,N) uint8
+    res.tracks.ids, res.tracks.age           # (B,N) int64 / int32 of those rows (-1 / 0: a dead slot); res.tracks.born (B) int32
+    res.count                                # (B) int32: the live tracks this pair started with
+    seq.tracks                               # the table after the advance: where the tracks are in the newest frame
 """
-from typing import NamedTuple, Optional
+from typing import Optional
 
 import torch
 
 from . import ops
 from .model import FF_RAFT_FUSION
+from .tracks import MAX_SLOTS, TrackResult, TrackTable
 
 
-class FrameResult(NamedTuple):
-    flow_low: torch.Tensor
-    flow_up: torch.Tensor
-    matches: Optional[torch.Tensor]
-    valid: Optional[torch.Tensor]
-    count: Optional[torch.Tensor]
+class FrameResult(tuple):
+    """(flow_low, flow_up, matches, valid, count): the named tuple a push returns.  In tracks mode it is a TrackedFrameResult, the
+    same with a sixth item `tracks` (a tracks.TrackResult); without tracks the tuple has the five items it always had, so a
+    caller that unpacks or walks them goes on working, and `.tracks` is None.  Both behave as typing.NamedTuple classes do:
+    `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
+    __slots__ = ()
+    _fields = ("flow_low", "flow_up", "matches", "valid", "count")
+
+    def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None):
+        if tracks is None:
+            return tuple.__new__(FrameResult, (flow_low, flow_up, matches, valid, count))
+        return tuple.__new__(TrackedFrameResult, (flow_low, flow_up, matches, valid, count, tracks))
+
+    flow_low = property(lambda self: self[0])
+    flow_up = property(lambda self: self[1])
+    matches = property(lambda self: self[2])
+    valid = property(lambda self: self[3])
+    count = property(lambda self: self[4])
+    tracks = property(lambda self: None)
+
+    def __getnewargs__(self):      # (copy, deepcopy and pickle rebuild through __new__, item by item)
+        return tuple(self)
+
+    @classmethod
+    def _make(cls, iterable):
+        return FrameResult(*iterable)
+
+    def _asdict(self):
+        return dict(zip(self._fields, self))
+
+    def _replace(self, **kwargs):
+        unknown = set(kwargs) - set(TrackedFrameResult._fields)
+        if unknown:
+            raise ValueError(f"Got unexpected field names: {sorted(unknown)!r}")
+        return FrameResult(**{**self._asdict(), **kwargs})
+
+    def __repr__(self):
+        return "FrameResult(" + ", ".join(f"{n}={v!r}" for n, v in zip(self._fields, self)) + ")"
+
+
+class TrackedFrameResult(FrameResult):
+    """A FrameResult of a session with tracks: six items, the last one `tracks`.  Made by FrameResult(..., tracks=...)."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("tracks",)
+    tracks = property(lambda self: self[5])
 
 
 class FrameSequence:
@@ -53,11 +102,20 @@ class FrameSequence:
     or (B,H,W), uint8 or fp32, unpadded: it is padded on the device and read when this frame is image1; `matches`, `valid`
     and `count` are then None.  mask2 is always None: init_mask overwrites it in every mode (ff_raft.py:23-72).
 
+    tracks=True (as many slots as det.max_corners) or tracks=N (1 .. 4096): the session keeps a tracks.TrackTable.  Behind the
+    detector the step replenishes it (ops.tracks_replenish: detections no nearer than det.min_distance to a live track take the
+    free slots and new ids), the model's mask1 becomes the rasterised TRACKS (ops.tracks_mask, padded as before) instead of the
+    detector's mask, and behind forward_interpolate the tracks advance by the flow at their sub-pixel positions
+    (ops.tracks_advance) in place of the matches at the detector's points.  `matches` and `valid` are then per slot, `count` is
+    the number of live tracks the pair started with, and the result carries `tracks` (ids and age of the rows, births).  reset()
+    empties the table and ids go on counting; a new shape drops it with the other buffers.
+
     The tensors of a result are the session's static buffers: valid until the next push.  A frame in pinned host memory is
     read by an asynchronous copy: leave it alone until work enqueued after the push has finished (the event a consumer
     waits for anyway before it reads the matches)."""
 
-    def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel"):
+    def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel",
+                 tracks=None):
         if not isinstance(model, FF_RAFT_FUSION):
             raise ValueError(f"model: FrameSequence drives FF_RAFT_FUSION, whose forward takes flow_init; {type(model).__name__} "
                              "(FF_PWCNET has no flow_init) runs pair by pair through graph.GraphedForward")
@@ -67,6 +125,13 @@ class FrameSequence:
             raise ValueError(f"order={order!r}: 'rgb' or 'bgr'")
         self.model, self.iters, self.warm_start, self.graph = model, raft_iters, bool(warm_start), bool(graph)
         self.keypoints, self.layout, self.order, self.pad_mode = keypoints, layout, order, pad_mode
+        self._slots = 0      # slots of the track table; 0: no tracks
+        if tracks is not None and tracks is not False:
+            if keypoints is None:
+                raise ValueError("tracks: a track table is replenished from a detector's points: give the session keypoints=GoodFeatures(...)")
+            self._slots = keypoints.max_corners if tracks is True else int(tracks)
+            if not 1 <= self._slots <= MAX_SLOTS or keypoints.max_corners > MAX_SLOTS:
+                raise ValueError(f"tracks: {self._slots} slots for a detector of max_corners={keypoints.max_corners}: both 1 .. {MAX_SLOTS}")
         self._reads_mask = getattr(model, "mask_modal", None) is not None
         self._require_eval()
         self._key = None
@@ -79,6 +144,7 @@ class FrameSequence:
     def _drop(self):
         self._cuda_graph = self._result = self._guard_words = None      # (the old graph's buffers go before the new ones come)
         self._u8 = self._mask_in = self._img1 = self._img2 = self._mask1 = self._mask_next = self._mask_det = self._flow_init = None
+        self._table = None
         self._frames = 0      # frames of the running sequence that have been ingested
 
     @property
@@ -93,11 +159,20 @@ class FrameSequence:
         warm_start or before the first frame."""
         return self._flow_init
 
+    @property
+    def tracks(self):
+        """The session's tracks.TrackTable, as the last pair's advance left it: positions in the newest frame.  None without
+        tracks= or before the first frame."""
+        return self._table
+
     def reset(self):
-        """A sequence boundary: the next push returns None and the pair after it starts cold."""
+        """A sequence boundary: the next push returns None and the pair after it starts cold, with an empty track table (ids
+        go on counting)."""
         self._frames = 0
         if self._flow_init is not None:
             self._flow_init.zero_()
+        if self._table is not None:
+            self._table.reset()
 
     # ---- inputs -----------------------------------------------------------------------------------------------------
     def _frame(self, frame):
@@ -152,6 +227,8 @@ class FrameSequence:
             self._mask_det = torch.zeros((b, 1, h, w), **f32)
         if self.warm_start:
             self._flow_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
+        if self._slots:
+            self._table = TrackTable(b, self._slots, device)
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -166,17 +243,24 @@ class FrameSequence:
         if self._mask_next is not None:
             self._mask1.copy_(self._mask_next)
         self._ingest()
-        det, points, count = self.keypoints, None, None
+        det, tb, points, count = self.keypoints, self._table, None, None
         if det is not None:
             inner = self._img1[:, :, top:top + h, left:left + w]      # (a dense innermost dimension: no copy)
             _, points, count = ops.good_features(inner, det.max_corners, det.quality_level, det.min_distance, out=self._mask_det,
                                                  return_points=True, ws=det._workspace(inner))
+            if tb is not None:
+                born, live = ops.tracks_replenish(tb.pos, tb.ids, tb.age, tb.next_id, points, count, h, w, det.min_distance)
+                if self._reads_mask:
+                    ops.tracks_mask(tb.pos, tb.ids, h, w, out=self._mask_det)      # (over the detector's mask: the model reads the tracks)
             if self._reads_mask:
                 ops.pad_replicate(self._mask_det, self.pad_mode, out=self._mask1)
         kw = dict(flow_init=self._flow_init) if self._flow_init is not None else {}
         flow_low, flow_up = self.model(self._img1, self._img2, self._mask1, None, raft_iters=self.iters, test_mode=True, **kw)
         if self.warm_start:
             ops.forward_interpolate(flow_low, out=self._flow_init)
+        if tb is not None:
+            matches, valid, ids, age = ops.tracks_advance(tb.pos, tb.ids, tb.age, flow_up, left, top, h, w)
+            return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, live, TrackResult(ids, age, born))
         matches = valid = None
         if det is not None:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
@@ -187,6 +271,7 @@ class FrameSequence:
         attributes, decide the routes and warm the allocator), what they changed put back, then the capture with static
         guard words."""
         keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init) if t is not None]
+        table = self._table.state() if self._table is not None else None      # (the warm-up steps would move tracks and spend ids)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -194,6 +279,8 @@ class FrameSequence:
                 self._step()
             for t, saved in keep:
                 t.copy_(saved)
+            if table is not None:
+                self._table.load_state(table)
         torch.cuda.current_stream().wait_stream(side)
         ops.guard_check(sync=True)
         self._guard_words = torch.zeros(2, dtype=torch.int32, device=self._img1.device) if ops.RANGE_GUARD else None

@@ -1131,6 +1131,93 @@ def keypoint_matches(points: Tensor, count: Tensor, flow_up: Tensor, left: int, 
     return out, valid
 
 
+def _track_table(name: str, pos: Tensor, ids: Tensor, age: Optional[Tensor] = None):
+    """The shapes of a track table's state (tracks.TrackTable): -> (B, N)."""
+    _require_device(pos, name, "pos", (torch.float32,))
+    _require_device(ids, name, "ids", (torch.int64,))
+    if pos.dim() != 3 or pos.shape[2] != 2 or not pos.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: pos must be contiguous (B,N,2), got {tuple(pos.shape)} strides {pos.stride()}")
+    b, n, _ = pos.shape
+    if tuple(ids.shape) != (b, n) or not ids.is_contiguous() or ids.device != pos.device:
+        raise _hip.FocusFlowHipError(f"{name}: ids must be contiguous {(b, n)} on {pos.device}, got {tuple(ids.shape)} strides {ids.stride()} on {ids.device}")
+    if age is not None:
+        _require_device(age, name, "age", (torch.int32,))
+        if tuple(age.shape) != (b, n) or not age.is_contiguous() or age.device != pos.device:
+            raise _hip.FocusFlowHipError(f"{name}: age must be contiguous {(b, n)} on {pos.device}, got {tuple(age.shape)} strides {age.stride()} on {age.device}")
+    return b, n
+
+
+def _track_outs(name: str, out, specs, device):
+    """out: None (new tensors) or one contiguous tensor per (what, shape, dtype) of `specs`, on `device`."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=device) for _, shape, dtype in specs)
+    if not isinstance(out, (tuple, list)) or len(out) != len(specs):
+        raise _hip.FocusFlowHipError(f"{name}: out must be the tuple ({', '.join(w for w, _, _ in specs)})")
+    for t, (what, shape, dtype) in zip(out, specs):
+        _require_device(t, name, f"out ({what})", (dtype,))
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+            raise _hip.FocusFlowHipError(f"{name}: out ({what}) must be contiguous {tuple(shape)} on {device}, got {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    return tuple(out)
+
+
+def tracks_replenish(pos: Tensor, ids: Tensor, age: Tensor, next_id: Tensor, points: Tensor, count: Tensor, h: int, w: int,
+                     min_distance: int, out=None):
+    """Fill the free slots of a track table with the detector's points (csrc/tracks.hip; the definition is in
+    include/focusflow_hip.h).  pos (B,N,2) fp32, ids (B,N) int64, age (B,N) int32, next_id (B) int64: the table, updated in
+    place; points (B,M,2) int32 and count (B) int32 as good_features(return_points=True) gives them, in coordinates of the h x w
+    frame.  A detection nearer than min_distance to a track that was live before the call is blocked; the others take the
+    free slots in ascending order and ids from next_id on.  -> (born (B) int32, live (B) int32); out: that tuple to write
+    into (default: new tensors).  Exact.  Enqueues only, so it can be captured."""
+    name = "tracks_replenish"
+    b, n = _track_table(name, pos, ids, age)
+    _require_device(next_id, name, "next_id", (torch.int64,))
+    _require_device(points, name, "points", (torch.int32,))
+    _require_device(count, name, "count", (torch.int32,))
+    for t, what in ((next_id, "next_id"), (points, "points"), (count, "count")):
+        if t.device != pos.device:
+            raise _hip.FocusFlowHipError(f"{name}: {what} is on {t.device}, the table on {pos.device}: one device expected")
+    if tuple(next_id.shape) != (b,) or not next_id.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: next_id must be contiguous ({b},), got {tuple(next_id.shape)}")
+    if points.dim() != 3 or points.shape[0] != b or points.shape[2] != 2 or not points.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: points must be contiguous ({b},M,2), got {tuple(points.shape)} strides {points.stride()}")
+    if tuple(count.shape) != (b,) or not count.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: count must be contiguous ({b},), got {tuple(count.shape)}")
+    born, live = _track_outs(name, out, (("born", (b,), torch.int32), ("live", (b,), torch.int32)), pos.device)
+    _hip.call("ff_tracks_replenish", _p(pos), _p(ids), _p(age), _p(next_id), n, _p(points), _p(count), points.shape[1], b, int(h), int(w),
+              int(min_distance), _p(born), _p(live), _stream())
+    return born, live
+
+
+def tracks_mask(pos: Tensor, ids: Tensor, h: int, w: int, out: Optional[Tensor] = None) -> Tensor:
+    """The live tracks as a key-point mask (csrc/tracks.hip): (B,1,h,w) fp32, 0 everywhere and 255 at the pixel nearest to
+    every live slot's position (floorf(x + 0.5f), clamped into the frame).  out: a contiguous (B,1,h,w) fp32 tensor (default: a
+    new one).  Enqueues only, so it can be captured."""
+    b, _ = _track_table("tracks_mask", pos, ids)
+    out = _padded_out("tracks_mask", out, (b, 1, int(h), int(w)), pos.device)
+    _hip.call("ff_tracks_mask", _p(pos), _p(ids), pos.shape[1], b, int(h), int(w), _p(out), _stream())
+    return out
+
+
+def tracks_advance(pos: Tensor, ids: Tensor, age: Tensor, flow_up: Tensor, left: int, top: int, h: int, w: int, out=None):
+    """Move every live track by the flow at its position (csrc/tracks.hip; the definition is in include/focusflow_hip.h).
+    The table (pos, ids, age) is updated in place; flow_up (B,2,Hp,Wp) fp32, any strides, the padded field whose h x w frame
+    starts at (left, top), sampled bilinearly in fp32 without leaving the frame.  -> (matches (B,N,4) fp32 [x, y, x', y'], valid
+    (B,N) uint8, ids (B,N) int64 and age (B,N) int32 as they were before the advance); rows of dead slots hold -1, 0, -1, 0.  A
+    track whose target leaves the frame (or is a NaN) dies.  out: that tuple of four to write into (default: new tensors).
+    Exact.  Enqueues only, so it can be captured."""
+    name = "tracks_advance"
+    b, n = _track_table(name, pos, ids, age)
+    _require_device(flow_up, name, "flow_up", (torch.float32,))
+    if flow_up.dim() != 4 or flow_up.shape[0] != b or flow_up.shape[1] != 2 or flow_up.device != pos.device:
+        raise _hip.FocusFlowHipError(f"{name}: flow_up must be ({b},2,Hp,Wp) on {pos.device}, got {tuple(flow_up.shape)} on {flow_up.device}")
+    hp, wp = flow_up.shape[2:]
+    matches, valid, ids_out, age_out = _track_outs(name, out, (("matches", (b, n, 4), torch.float32), ("valid", (b, n), torch.uint8),
+                                                               ("ids", (b, n), torch.int64), ("age", (b, n), torch.int32)), pos.device)
+    _hip.call("ff_tracks_advance", _p(pos), _p(ids), _p(age), n, _p(flow_up), flow_up.stride(0), flow_up.stride(1), flow_up.stride(2), flow_up.stride(3),
+              b, int(left), int(top), int(h), int(w), hp, wp, _p(matches), _p(valid), _p(ids_out), _p(age_out), _stream())
+    return matches, valid, ids_out, age_out
+
+
 def coords_step(coords1: Tensor, delta: Optional[Tensor], flow4: Optional[Tensor], slot: Optional[Tensor]):
     b, h, w, _ = coords1.shape
     _hip.call("ff_coords_step", _p(coords1), _p(delta), _ld(delta) if delta is not None else 0, _p(flow4), _p(slot),

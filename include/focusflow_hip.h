@@ -63,7 +63,9 @@ const char* ff_last_error(void);
  *   7 (unchanged): entry points only: ff_frame_ingest, ff_pad_replicate, ff_keypoint_matches (video sessions: uint8 frames
  *                in, key-point matches out).  No struct or argument list changed, so a caller built against an earlier 7 is
  *                still right; a caller that needs these three finds out from the symbols (the Python binding names the
- *                missing one and asks for a rebuild) */
+ *                missing one and asks for a rebuild)
+ *   7 (unchanged): entry points only: ff_tracks_replenish, ff_tracks_mask, ff_tracks_advance (key-point tracks with
+ *                persistent ids across the frames of a video session) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -419,6 +421,43 @@ int ff_pad_replicate(const void* src, int src_is_u8, long long ld_b, long long l
 int ff_keypoint_matches(const int* points, const int* count, int N, const float* flow_up, long long ld_b, long long ld_c, long long ld_row,
                         long long ld_col, int B, int left, int top, int H, int W, int Hp, int Wp, float* matches, unsigned char* valid,
                         void* stream);
+/* Key-point tracks: a table of N slots per sample (1 <= N <= 4096) that follows points over the frames of a video and gives
+ * each a persistent id.  State, all contiguous and updated in place:
+ *   pos (B,N,2) fp32 [x, y] in coordinates of the unpadded H x W frame; ids (B,N) int64; age (B,N) int32; next_id (B) int64
+ *   a dead slot: ids = -1, pos = -1, age = 0; a live slot (ids >= 0) keeps 0 <= x <= W - 1 and 0 <= y <= H - 1
+ * Every step is exact, so the results have no tolerance (tests/tracks_ref.py restates them in numpy).
+ *
+ * ff_tracks_replenish: fill free slots with the detector's points.  points (B,M,2) int32 [x, y] and count (B) int32 as
+ * ff_good_features writes them (acceptance order = descending strength), M <= 4096; count is clamped to 0 .. M.  Detection
+ * j < count[b] inside the frame is BLOCKED iff a slot that was live before the call has dx dx + dy dy < (double) min_distance^2,
+ * dx = (double) pos_x - (double) x_j, dy likewise, in fp64 with every operation rounded separately (min_distance = 0 blocks
+ * nothing).  The unblocked detections, in detector order, take the free slots in ascending slot index until either runs
+ * out; the r-th taken (from 0) gets ids = next_id[b] + r, pos = ((float) x, (float) y), age = 0.  Then next_id[b] += the
+ * number taken = born[b], and live[b] = the live slots afterwards.  Births do not block each other (the detector spaced
+ * them); a detection outside the frame is passed over.  One launch, one block per sample.
+ *
+ * ff_tracks_mask: mask (B,1,H,W) fp32 contiguous, 16-byte aligned = 0 everywhere and 255 at (floorf(x + 0.5f), floorf(y + 0.5f)),
+ * clamped into the frame, of every live slot.  Two launches (zero, scatter).
+ *
+ * ff_tracks_advance: move every live slot by the flow sampled bilinearly at its position.  flow_up is addressed as in
+ * ff_keypoint_matches (element strides, frame at (left, top) of the padded Hp x Wp field); taps never leave the H x W frame:
+ *   x0 = (int) floorf(x) clamped to 0 .. W - 1, x1 = min(x0 + 1, W - 1), fx = x - (float) x0; the same for y;
+ *   in fp32, each operation rounded separately: wx0 = 1 - fx; top = wx0 f00 + fx f01; bot = wx0 f10 + fx f11; wy0 = 1 - fy;
+ *   u = wy0 top + fy bot; the same for v; x' = x + u, y' = y + v (one fp32 add each)
+ *   matches[b][s] = [x, y, x', y']; valid[b][s] = 1 iff 0 <= x' <= W - 1 and 0 <= y' <= H - 1 (a NaN gives 0);
+ *   ids_out / age_out = the slot's id and age BEFORE the advance
+ * A valid slot moves to (x', y') and its age += 1; an invalid one dies.  Rows of slots that were dead already hold -1, 0, -1,
+ * 0.  On integer positions fx = fy = 0 and the match equals ff_keypoint_matches' as a value.  matches (B,N,4) fp32 contiguous,
+ * 16-byte aligned; valid (B,N) uint8; ids_out (B,N) int64; age_out (B,N) int32.  One launch, one thread per slot.
+ *
+ * All three enqueue only (capturable), allocate nothing and use no atomics.  Refused (FF_EINVAL): a null pointer, N or M
+ * outside 1 .. 4096, min_distance outside 0 .. 32, B, H or W < 1, H or W > 2^24, left or top < 0, left + W > Wp, top + H > Hp. */
+int ff_tracks_replenish(float* pos, long long* ids, int* age, long long* next_id, int N, const int* points, const int* count, int M,
+                        int B, int H, int W, int min_distance, int* born, int* live, void* stream);
+int ff_tracks_mask(const float* pos, const long long* ids, int N, int B, int H, int W, float* mask, void* stream);
+int ff_tracks_advance(float* pos, long long* ids, int* age, int N, const float* flow_up, long long ld_b, long long ld_c,
+                      long long ld_row, long long ld_col, int B, int left, int top, int H, int W, int Hp, int Wp, float* matches,
+                      unsigned char* valid, long long* ids_out, int* age_out, void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
