@@ -30,6 +30,15 @@ class FFFusionPair(C.Structure):
     ]
 
 
+class FFEncoderTail(C.Structure):
+    """include/focusflow_hip.h: FFEncoderTail (ff_encoder_tail_fwd)."""
+    _fields_ = [
+        ("x", _fp * 2), ("x_ld", C.c_int * 2), ("xres", _fp * 2), ("xres_ld", C.c_int * 2), ("scale", _fp * 2), ("shift", _fp * 2),
+        ("in_act", C.c_int), ("w_frag", _fp), ("bias", _fp), ("w_format", C.c_int), ("y", _fp), ("y_ld", C.c_int),
+        ("B", C.c_int), ("HW", C.c_int), ("C", C.c_int), ("Cout", C.c_int),
+    ]
+
+
 class FFConvParams(C.Structure):
     _fields_ = [
         ("x", _fp * MAX_SEG), ("x_ld", C.c_int * MAX_SEG), ("x_c", C.c_int * MAX_SEG),
@@ -121,6 +130,7 @@ _SIGS = {
     "ff_gru_pass_rec": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                         _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_fusion_pair_fwd": [C.POINTER(FFFusionPair), _fp],
+    "ff_encoder_tail_fwd": [C.POINTER(FFEncoderTail), _fp],
     "ff_gru_rh": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _ll, C.c_int, _fp],
     "ff_gru_blend": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _ll, C.c_int, _fp],
     "ff_upsample_flow": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp],

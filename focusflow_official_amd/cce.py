@@ -392,6 +392,8 @@ def _branch_stream(device):
 
 _FUSION_PAIR = os.environ.get("FF_FUSION_PAIR", "1") != "0"   # fusion units 1-3 as ff_fusion_pair_fwd launches with lazy normalised inputs (inference; A/B switch)
 _PAIR_FUSION = True       # both 1x1 convs of a fusion unit in one launch where ff_fusion_pair_fwd has no instance (inference)
+_ENCODER_TAIL = True      # fusion4, conv2 / mask_conv2 and fusion5 as ONE launch with a composed weight (csrc/encoder_tail.hip; inference)
+_W_LIMIT = 4094.0         # |w| of a packed split row stays below this (csrc/ff_common.h)
 
 
 def invalidate_packed(module: nn.Module) -> int:
@@ -412,6 +414,9 @@ def invalidate_packed(module: nn.Module) -> int:
             n += 1
         if getattr(m, "_pair_key", None) is not None:
             m._pair_key = None
+            n += 1
+        if getattr(m, "_tail_key", None) is not None:           # BasicParallelFusionLayer's composed output-stage weight
+            m._tail_key = None
             n += 1
         if getattr(m, "_mask2_stage_of", None) is not None:     # BasicUpdateBlock.upsample's stage-major image of mask[2]
             m._mask2_stage = m._mask2_stage_of = None
@@ -781,6 +786,43 @@ class BasicParallelFusionLayer(_ResidualEncoder):
         probe = torch.empty((1, h, w, c), device="meta")
         return unit._pair_kernel_ok(probe)
 
+    def _tail_eligible(self) -> bool:
+        """ff_encoder_tail_fwd may take the output stage: inference, a split weight format, 1x1 fusion units, 128 + 128 -> 256."""
+        return (_ENCODER_TAIL and not torch.is_grad_enabled() and ops.w_format() in (_hip.W_F16X3, _hip.W_F16)
+                and self.fusion_type in ("1x1conv", "1x1conv-unidirection") and self.fusion5.img2mask is None
+                and (self.conv2.in_channels, self.conv2.out_channels) == (128, 256) and self.conv2.weight.is_cuda)
+
+    def _tail_weights(self):
+        """The output stage as one 1x1 convolution over the segments [x | m] (parallel_fusion.py:237-242 has no activation
+        and no norm between fusion4, conv2 / mask_conv2 and fusion5):
+            out = (Wx + A5 Wm B4) x + (Wx A4 + A5 Wm) m + (Wx a4 + bx + A5 (Wm b4 + bm) + a5)
+        composed in float64, rounded once to fp32 and packed like any 1x1 weight (split rows in fragment order) -> (w_frag, bias),
+        or None where a composed weight reaches the split format's limit (the stage then keeps its separate launches).  Rebuilt
+        when a parameter changes (the cache key of FusionUnit._paired); building it reads one number back, so a miss while a
+        hipGraph is being captured also means None - the warm-up forwards in front of a capture fill the cache."""
+        f4, f5 = self.fusion4, self.fusion5
+        convs = [f4.mask2img.conv, self.conv2, self.mask_conv2, f5.mask2img.conv] + ([f4.img2mask.conv] if f4.img2mask is not None else [])
+        key = (ops.conv_precision(),) + tuple((t._version, t.data_ptr()) for cv in convs for t in (cv._parameters["weight"], cv._parameters["bias"]))
+        if getattr(self, "_tail_key", None) != key:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            w64 = lambda cv: cv.weight.detach().double().flatten(1)        # noqa: E731
+            b64 = lambda cv: cv.bias.detach().double()                     # noqa: E731
+            a4, wx, wm, a5 = (w64(cv) for cv in convs[:4])
+            w_x, w_m, bm = wx, wx @ a4 + a5 @ wm, b64(self.mask_conv2)
+            if f4.img2mask is not None:         # ('1x1conv-unidirection' has no img -> mask direction: B4 = 0, b4 = 0)
+                w_x = wx + a5 @ (wm @ w64(f4.img2mask.conv))
+                bm = wm @ b64(f4.img2mask.conv) + bm
+            bias = wx @ b64(f4.mask2img.conv) + b64(self.conv2) + a5 @ bm + b64(f5.mask2img.conv)
+            wf = torch.cat([w_x, w_m], 1).float()                          # rounded once
+            self._tail = None
+            if float(wf.abs().max()) < _W_LIMIT:
+                rows = torch.empty_like(wf)
+                ops.pack_conv_weight(wf[:, :, None, None].contiguous(), rows, wf.shape[1], 0)
+                self._tail = (ops.pack_frag16(ops.pack_split(rows), wf.shape[0]), bias.float().contiguous())
+            self._tail_key = key
+        return self._tail
+
     def forward(self, x, mask):
         b, hh, ww = x.shape[0], x.shape[1], x.shape[2]
         lz1 = self._lazy_for(self.fusion1, 64, hh // 2, ww // 2)
@@ -793,7 +835,13 @@ class BasicParallelFusionLayer(_ResidualEncoder):
         m, x = self.fusion2.run(m, x)
         m, x = self._branches(lambda t: self._run_stage(self.mask_layer2, t, lz3), lambda t: self._run_stage(self.layer2, t, lz3), m, x)
         m, x = self.fusion3.run(m, x)
-        m, x = self._branches(lambda t: self._run_stage(self.mask_layer3, t), lambda t: self._run_stage(self.layer3, t), m, x)
+        # the output stage - fusion4, the two output convolutions, fusion5 - is linear: one launch with a composed weight
+        # where the kernel takes it (inference); stage 3's last normalisation pass is then left to its loader as well
+        tail = self._tail_weights() if self._tail_eligible() else None
+        lz4 = tail is not None and self.norm_fn == "instance"
+        m, x = self._branches(lambda t: self._run_stage(self.mask_layer3, t, lz4), lambda t: self._run_stage(self.layer3, t, lz4), m, x)
+        if tail is not None and ops.encoder_tail_inputs_ok(x, m):
+            return ops.encoder_tail(x, m, tail[0], tail[1], ops.w_format())
         m, x = self.fusion4.run(m, x)
         m, x = fn.conv(self._mout, m), self._run_out(x)
         m, x = self.fusion5.run(m, x)

@@ -1342,6 +1342,53 @@ def fusion_pair(img, mask, w_frag, bias, w_fmt: int):
     return outs[0], outs[1]
 
 
+def encoder_tail_inputs_ok(*ins) -> bool:
+    """ff_encoder_tail_fwd reads two contiguous NHWC tensors of 128 channels (fp32 or LazyAct) on the device; its 256-channel
+    output stays below 2 GiB."""
+    if not fusion_pair_inputs_ok(*ins) or ins[0].shape != ins[1].shape:
+        return False
+    b, h, w, c = ins[0].shape
+    return c == 128 and b * h * w * 256 * 4 < (1 << 31) and all((v.t if isinstance(v, LazyAct) else v).dtype == torch.float32 for v in ins)
+
+
+def encoder_tail(x, m, w_frag: Tensor, bias: Tensor, w_fmt: int) -> Tensor:
+    """The output stage of a CCE encoder - fusion4, conv2 / mask_conv2, fusion5 - as ONE launch (ff_encoder_tail_fwd):
+    x / m the two stage-3 outputs (fp32 NHWC, 128 channels, or LazyAct); w_frag the composed 256 x 256 weight over the segments
+    [x | m] in fragment order, bias [256] -> (B, H, W, 256).  What the kernel cannot read is refused by the library."""
+    ins = (x, m)
+    b, h, w, c = ins[0].shape
+    p = _hip.FFEncoderTail()
+    for i, v in enumerate(ins):
+        t = v.t if isinstance(v, LazyAct) else v
+        _require_gpu(t)
+        if tuple(t.shape[:3]) != (b, h, w):
+            raise _hip.FocusFlowHipError(f"encoder_tail: inputs of different shapes {tuple(ins[0].shape)} / {tuple(t.shape)}")
+        c = min(c, t.shape[3])
+        p.x[i], p.x_ld[i] = t.data_ptr(), _ld(t)
+        if isinstance(v, LazyAct):
+            sc, sh = v.coeffs()
+            p.scale[i], p.shift[i] = sc.data_ptr(), sh.data_ptr()
+            p.in_act = v.act
+            if v.res is not None:
+                p.xres[i], p.xres_ld[i] = v.res.data_ptr(), _ld(v.res)
+    acts = {v.act for v in ins if isinstance(v, LazyAct)}
+    assert len(acts) <= 1, "lazy inputs of one stage share the activation"
+    if _range_word is not None:      # CHECK_RANGE: as fusion_pair - a lazy value is bounded by its residual
+        for v in ins:
+            probe = v.res if isinstance(v, LazyAct) else v
+            if probe is not None:
+                _range_probe(probe)
+    _require_gpu(bias)
+    cout = bias.numel()
+    y = empty_nhwc(b, h, w, cout, bias)
+    p.w_frag, p.bias, p.w_format = w_frag.data_ptr(), bias.data_ptr(), w_fmt
+    p.y, p.y_ld = y.data_ptr(), cout
+    p.B, p.HW, p.C, p.Cout = b, h * w, c, cout
+    # (timed with the convolutions in bench.py's roofline_conv: one 2C -> Cout 1x1 convolution, the FLOP the kernel issues)
+    _timed_call("conv", "ff_encoder_tail_fwd", C.byref(p), _stream(), note=(2.0 * b * h * w * 2 * c * cout, w_fmt))
+    return y
+
+
 def mask_upsample_pack(w_split: Tensor) -> Tensor:
     """Split rows of the mask head's second convolution (576 x 256) -> ff_mask_upsample_fwd's stage-major weight image."""
     assert w_split.dtype == torch.uint8 and w_split.numel() == 576 * 1024 and w_split.is_contiguous()

@@ -65,7 +65,8 @@ const char* ff_last_error(void);
  *                still right; a caller that needs these three finds out from the symbols (the Python binding names the
  *                missing one and asks for a rebuild)
  *   7 (unchanged): entry points only: ff_tracks_replenish, ff_tracks_mask, ff_tracks_advance (key-point tracks with
- *                persistent ids across the frames of a video session) */
+ *                persistent ids across the frames of a video session)
+ *   7 (unchanged): entry point only: ff_encoder_tail_fwd (FFEncoderTail: the encoders' output stage as one launch) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -510,6 +511,29 @@ typedef struct FFFusionPair {
 } FFFusionPair;
 int ff_fusion_pair_tile(int C);
 int ff_fusion_pair_fwd(const FFFusionPair* p, void* stream);
+/* ------------------------------------------------------------------------
+ * The output stage of a Condition Control Encoder (parallel_fusion.py:237-242: fusion4, conv2 / mask_conv2, fusion5 - linear
+ * from end to end) as one 1x1 convolution over the segments [v0 | v1] of the two stage-3 outputs (csrc/encoder_tail.hip):
+ *     y = W [v0 | v1] + bias
+ * W: the composed 256 x 256 weight (cce.py) as split rows re-ordered by ff_pack_frag16 (8 K chunks: v0's channels first);
+ * bias: [256].  Branch i's value v_i is x[i] itself or - LAZY inputs, scale[i] != NULL - as in FFFusionPair:
+ *     t = in_act(fma(x[i], scale[i][b][c], shift[i][b][c]))  ;  v_i = xres[i] ? relu(xres[i] + t) : t
+ * the operations of ff_norm_apply, bit for bit.  C = 128 channels per branch, Cout = 256; B images of HW pixels (any HW: a
+ * partial last tile is bounded by the kernel); x / xres / y contiguous NHWC fp32 (x_ld = xres_ld = 128, y_ld = 256), 16-byte
+ * aligned, y below 2 GiB and no alias of an input; w_format FF_W_F16X3 / FF_W_F16.  Anything else is refused.
+ * ---------------------------------------------------------------------- */
+typedef struct FFEncoderTail {
+    const float* x[2];     int x_ld[2];       /* [0] the frame branch, [1] the condition (mask) branch */
+    const float* xres[2];  int xres_ld[2];
+    const float* scale[2]; const float* shift[2];
+    int in_act;                      /* FF_ACT_* applied to fma(x, scale, shift) */
+    const void* w_frag;
+    const float* bias;
+    int w_format;
+    float* y;              int y_ld;
+    int B, HW, C, Cout;
+} FFEncoderTail;
+int ff_encoder_tail_fwd(const FFEncoderTail* p, void* stream);
 /* GRU gates (update.py:47-49): rh = r*h ; h' = (1-z)*h + z*q */
 int ff_gru_rh(const float* r, int r_ld, const float* h, int h_ld, float* rh, int rh_ld,
               long long npix, int C, void* stream);
