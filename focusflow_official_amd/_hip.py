@@ -124,6 +124,10 @@ _SIGS = {
     "ff_tracks_mask": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp],
     "ff_tracks_advance": [_fp, _fp, _fp, C.c_int, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp,
                           _fp, _fp],
+    "ff_fb_dense": [_fp, _ll, _ll, _ll, _ll, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                    _fp, _fp, _fp],
+    "ff_fb_matches": [_fp, _fp, C.c_int, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                      _fp, _fp, _fp, _fp, _fp, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],

@@ -21,8 +21,19 @@ With tracks (tracks.TrackTable, csrc/tracks.hip) the session follows its key poi
     res.tracks.ids, res.tracks.age           # (B,N) int64 / int32 of those rows (-1 / 0: a dead slot); res.tracks.born (B) int32
     res.count                                # (B) int32: the live tracks this pair started with
     seq.tracks                               # the table after the advance: where the tracks are in the newest frame
+
+With fb=True (or fb=FBCheck(alpha, beta, iters, warm)) the step also computes the BACKWARD flow of the pair and holds the
+forward flow to it (csrc/fb_check.hip): a point whose round trip does not end where it began is occluded or sits on a bad vector.
+
+    seq = FrameSequence(model, raft_iters=12, keypoints=GoodFeatures(), tracks=True, fb=True)
+    res = seq.push(frame)
+    res.fb.flow_bw, res.fb.err2, res.fb.occluded    # (B,2,H,W) flow(this -> previous); (B,1,H,W) fp32 squared round-trip error in
+                                                    # px^2 (+inf: the target left the frame); (B,1,H,W) uint8 occlusion map
+    res.fb.point_err2, res.fb.status         # per row of res.matches: (B,N) fp32, (B,N) uint8 (0 no row, 1 consistent, 2 the target
+                                             # left the frame, 3 inconsistent); res.valid is 1 only where the status is 1, and
+                                             # with tracks the slots of status 3 have died: the next replenish refills them
 """
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -31,18 +42,46 @@ from .model import FF_RAFT_FUSION
 from .tracks import MAX_SLOTS, TrackResult, TrackTable
 
 
+class FBCheck(NamedTuple):
+    """The forward-backward check of a session (FrameSequence(fb=...)).  A point is inconsistent where the squared round-trip
+    error exceeds alpha (|forward|^2 + |backward|^2) + beta (px^2); the defaults are the occlusion criterion of UnFlow (Meister
+    et al. 2018).  iters: the update iterations of the backward flow (None: the session's raft_iters); warm: start the backward
+    flow from the negated forward_interpolate of the forward flow instead of from zero."""
+    alpha: float = 0.01
+    beta: float = 0.5
+    iters: Optional[int] = None
+    warm: bool = True
+
+
+class FBResult(NamedTuple):
+    """What a pair adds to a FrameResult in a session with fb=: the backward flow as the (B,2,H,W) unpadded view, the dense
+    squared round-trip error (B,1,H,W) fp32 and occlusion map (B,1,H,W) uint8, and per row of `matches` the error (B,N) fp32 and
+    the status (B,N) uint8 (None without matches).  Session buffers: valid until the next push."""
+    flow_bw: torch.Tensor
+    err2: torch.Tensor
+    occluded: torch.Tensor
+    point_err2: Optional[torch.Tensor]
+    status: Optional[torch.Tensor]
+
+
 class FrameResult(tuple):
     """(flow_low, flow_up, matches, valid, count): the named tuple a push returns.  In tracks mode it is a TrackedFrameResult, the
-    same with a sixth item `tracks` (a tracks.TrackResult); without tracks the tuple has the five items it always had, so a
-    caller that unpacks or walks them goes on working, and `.tracks` is None.  Both behave as typing.NamedTuple classes do:
-    `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
+    same with a sixth item `tracks` (a tracks.TrackResult); in a session with fb= it carries a trailing item `fb` (an FBResult)
+    behind those: a CheckedFrameResult (six items) or a TrackedCheckedFrameResult (seven).  Without either the tuple has the five
+    items it always had, so a caller that unpacks or walks them goes on working, and `.tracks` and `.fb` are None.  All four
+    behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
     __slots__ = ()
     _fields = ("flow_low", "flow_up", "matches", "valid", "count")
 
-    def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None):
+    def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None, fb: Optional[FBResult] = None):
+        items = (flow_low, flow_up, matches, valid, count)
+        if tracks is None and fb is None:
+            return tuple.__new__(FrameResult, items)
+        if fb is None:
+            return tuple.__new__(TrackedFrameResult, items + (tracks,))
         if tracks is None:
-            return tuple.__new__(FrameResult, (flow_low, flow_up, matches, valid, count))
-        return tuple.__new__(TrackedFrameResult, (flow_low, flow_up, matches, valid, count, tracks))
+            return tuple.__new__(CheckedFrameResult, items + (fb,))
+        return tuple.__new__(TrackedCheckedFrameResult, items + (tracks, fb))
 
     flow_low = property(lambda self: self[0])
     flow_up = property(lambda self: self[1])
@@ -50,19 +89,24 @@ class FrameResult(tuple):
     valid = property(lambda self: self[3])
     count = property(lambda self: self[4])
     tracks = property(lambda self: None)
+    fb = property(lambda self: None)
 
     def __getnewargs__(self):      # (copy, deepcopy and pickle rebuild through __new__, item by item)
-        return tuple(self)
+        return tuple(self[:5]) + (self.tracks, self.fb)
 
     @classmethod
     def _make(cls, iterable):
-        return FrameResult(*iterable)
+        """From the items of any of the four shapes; a sixth item is `fb` if it is an FBResult, else `tracks`."""
+        items = tuple(iterable)
+        if len(items) == 6 and isinstance(items[5], FBResult):
+            return FrameResult(*items[:5], fb=items[5])
+        return FrameResult(*items)
 
     def _asdict(self):
         return dict(zip(self._fields, self))
 
     def _replace(self, **kwargs):
-        unknown = set(kwargs) - set(TrackedFrameResult._fields)
+        unknown = set(kwargs) - set(TrackedCheckedFrameResult._fields)
         if unknown:
             raise ValueError(f"Got unexpected field names: {sorted(unknown)!r}")
         return FrameResult(**{**self._asdict(), **kwargs})
@@ -76,6 +120,21 @@ class TrackedFrameResult(FrameResult):
     __slots__ = ()
     _fields = FrameResult._fields + ("tracks",)
     tracks = property(lambda self: self[5])
+
+
+class CheckedFrameResult(FrameResult):
+    """A FrameResult of a session with fb= and no tracks: six items, the last one `fb`.  Made by FrameResult(..., fb=...)."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("fb",)
+    fb = property(lambda self: self[5])
+
+
+class TrackedCheckedFrameResult(FrameResult):
+    """A FrameResult of a session with tracks and fb=: seven items, `tracks` and `fb` last.  Made by FrameResult(..., tracks=..., fb=...)."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("tracks", "fb")
+    tracks = property(lambda self: self[5])
+    fb = property(lambda self: self[6])
 
 
 class FrameSequence:
@@ -110,12 +169,22 @@ class FrameSequence:
     the number of live tracks the pair started with, and the result carries `tracks` (ids and age of the rows, births).  reset()
     empties the table and ids go on counting; a new shape drops it with the other buffers.
 
+    fb=True or fb=FBCheck(...): behind the advance (or the matches) the step runs the model a second time, on (image2, image1),
+    and checks the forward flow against that backward flow.  Its mask (for models that read one) is `fb_mask`: with tracks the
+    rasterised table as the advance left it - the points being followed, now in the newest frame -, with a detector alone the
+    detector run on image2, with caller-supplied masks the mask that came with this frame.  With FBCheck.warm it starts from the
+    negated forward_interpolate of the forward flow (the splatted forward flow sits at its targets, and the backward flow is
+    about minus that), in a buffer of its own.  Then ops.fb_dense writes the squared round-trip error and the occlusion map of
+    every pixel, and ops.fb_matches the error and status of every match row; it clears `valid` where the round trip is
+    inconsistent and, with tracks, kills those slots: the table the next pair starts from is the culled one, and the next
+    replenish refills what the check freed.  The result then carries a trailing `fb` (an FBResult).
+
     The tensors of a result are the session's static buffers: valid until the next push.  A frame in pinned host memory is
     read by an asynchronous copy: leave it alone until work enqueued after the push has finished (the event a consumer
     waits for anyway before it reads the matches)."""
 
     def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel",
-                 tracks=None):
+                 tracks=None, fb=None):
         if not isinstance(model, FF_RAFT_FUSION):
             raise ValueError(f"model: FrameSequence drives FF_RAFT_FUSION, whose forward takes flow_init; {type(model).__name__} "
                              "(FF_PWCNET has no flow_init) runs pair by pair through graph.GraphedForward")
@@ -132,6 +201,15 @@ class FrameSequence:
             self._slots = keypoints.max_corners if tracks is True else int(tracks)
             if not 1 <= self._slots <= MAX_SLOTS or keypoints.max_corners > MAX_SLOTS:
                 raise ValueError(f"tracks: {self._slots} slots for a detector of max_corners={keypoints.max_corners}: both 1 .. {MAX_SLOTS}")
+        self.fb = None      # the FBCheck of the session; None: no forward-backward check
+        if fb is not None and fb is not False:
+            self.fb = FBCheck() if fb is True else fb
+            if not isinstance(self.fb, FBCheck):
+                raise ValueError(f"fb: True or a frames.FBCheck(alpha, beta, iters, warm) expected, got {type(fb).__name__}")
+            if not (self.fb.alpha >= 0 and self.fb.beta >= 0):
+                raise ValueError(f"fb: alpha={self.fb.alpha}, beta={self.fb.beta}: both >= 0 (and no NaN)")
+            if self.fb.iters is not None and int(self.fb.iters) < 1:
+                raise ValueError(f"fb: iters={self.fb.iters}: None (the session's raft_iters) or at least 1")
         self._reads_mask = getattr(model, "mask_modal", None) is not None
         self._require_eval()
         self._key = None
@@ -145,6 +223,7 @@ class FrameSequence:
         self._cuda_graph = self._result = self._guard_words = None      # (the old graph's buffers go before the new ones come)
         self._u8 = self._mask_in = self._img1 = self._img2 = self._mask1 = self._mask_next = self._mask_det = self._flow_init = None
         self._table = None
+        self._fb_mask = self._fb_mask_det = self._fb_init = self._guard_words_bw = None
         self._frames = 0      # frames of the running sequence that have been ingested
 
     @property
@@ -165,12 +244,22 @@ class FrameSequence:
         tracks= or before the first frame."""
         return self._table
 
+    @property
+    def fb_mask(self):
+        """The padded (B,1,Hp,Wp) mask the last pair's BACKWARD forward read for its first frame, the newest one; None without
+        fb=, before the first pair and for plain RAFT."""
+        if self.fb is None or not self._reads_mask or self._frames < 2:
+            return None
+        return self._fb_mask if self._fb_mask is not None else self._mask_next      # (caller-supplied: the mask that came with this frame)
+
     def reset(self):
         """A sequence boundary: the next push returns None and the pair after it starts cold, with an empty track table (ids
         go on counting)."""
         self._frames = 0
         if self._flow_init is not None:
             self._flow_init.zero_()
+        if self._fb_init is not None:
+            self._fb_init.zero_()
         if self._table is not None:
             self._table.reset()
 
@@ -229,6 +318,12 @@ class FrameSequence:
             self._flow_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
         if self._slots:
             self._table = TrackTable(b, self._slots, device)
+        if self.fb is not None:
+            if self._reads_mask and self.keypoints is not None:      # (with caller-supplied masks the backward mask is _mask_next)
+                self._fb_mask_det, self._fb_mask = torch.zeros((b, 1, h, w), **f32), torch.zeros((b, 1, hp, wp), **f32)
+            if self.fb.warm:
+                self._fb_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
+                ops.negate(self._fb_init, self._fb_init)      # (makes the constant negate() reads now, not inside a capture)
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -258,13 +353,54 @@ class FrameSequence:
         flow_low, flow_up = self.model(self._img1, self._img2, self._mask1, None, raft_iters=self.iters, test_mode=True, **kw)
         if self.warm_start:
             ops.forward_interpolate(flow_low, out=self._flow_init)
+        matches = valid = tracks = None
         if tb is not None:
             matches, valid, ids, age = ops.tracks_advance(tb.pos, tb.ids, tb.age, flow_up, left, top, h, w)
-            return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, live, TrackResult(ids, age, born))
-        matches = valid = None
-        if det is not None:
+            count, tracks = live, TrackResult(ids, age, born)
+        elif det is not None:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
-        return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, count)
+        fb = self._check(flow_low, flow_up, matches, valid) if self.fb is not None else None
+        return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, count, tracks, fb)
+
+    def _check(self, flow_low, flow_up, matches, valid):
+        """The forward-backward part of a step, behind the advance / the matches: the backward pair's mask, the backward flow's
+        start, the backward flow, the dense check, the point check (which clears `valid` and culls the table).  -> FBResult."""
+        b, h, w = self._bhw
+        left, top, hp, wp = self._pad
+        fb, det, tb = self.fb, self.keypoints, self._table
+        mask = None
+        if self._reads_mask:
+            if det is None:
+                mask = self._mask_next
+            else:
+                if tb is not None:      # the table as the advance left it, before any culling: the tracks in the newest frame
+                    ops.tracks_mask(tb.pos, tb.ids, h, w, out=self._fb_mask_det)
+                else:
+                    inner = self._img2[:, :, top:top + h, left:left + w]
+                    ops.good_features(inner, det.max_corners, det.quality_level, det.min_distance, out=self._fb_mask_det, ws=det._workspace(inner))
+                mask = ops.pad_replicate(self._fb_mask_det, self.pad_mode, out=self._fb_mask)
+        kw = {}
+        if fb.warm:
+            if self.warm_start:      # (flow_init holds forward_interpolate(flow_low) already)
+                ops.negate(self._flow_init, self._fb_init)
+            else:
+                ops.negate(ops.forward_interpolate(flow_low, out=self._fb_init), self._fb_init)
+            kw = dict(flow_init=self._fb_init)
+        # a captured forward zeroes and fills the capture's guard words: the backward one gets a pair of its own
+        st = ops._guard_state()
+        words = st["capture_words"]
+        if words is not None and self._guard_words_bw is not None:
+            st["capture_words"] = self._guard_words_bw
+        try:
+            _, flow_bw = self.model(self._img2, self._img1, mask, None, raft_iters=self.iters if fb.iters is None else int(fb.iters), test_mode=True, **kw)
+        finally:
+            st["capture_words"] = words
+        err2, occluded = ops.fb_dense(flow_up, flow_bw, left, top, h, w, fb.alpha, fb.beta)
+        point_err2 = status = None
+        if matches is not None:
+            point_err2, status = ops.fb_matches(matches, valid, flow_bw, left, top, h, w, fb.alpha, fb.beta,
+                                                table=None if tb is None else (tb.pos, tb.ids, tb.age))
+        return FBResult(flow_bw[:, :, top:top + h, left:left + w], err2, occluded, point_err2, status)
 
     def _capture(self, warmup=3):
         """graph.GraphedForward's capture around `_step`: warm-up steps on a side stream (they pack weights, set kernel
@@ -284,6 +420,7 @@ class FrameSequence:
         torch.cuda.current_stream().wait_stream(side)
         ops.guard_check(sync=True)
         self._guard_words = torch.zeros(2, dtype=torch.int32, device=self._img1.device) if ops.RANGE_GUARD else None
+        self._guard_words_bw = torch.zeros(2, dtype=torch.int32, device=self._img1.device) if ops.RANGE_GUARD and self.fb is not None else None
         st = ops._guard_state()
         st["capture_words"] = self._guard_words
         self._cuda_graph = torch.cuda.CUDAGraph()
@@ -324,4 +461,6 @@ class FrameSequence:
             self._cuda_graph.replay()
             if self._guard_words is not None:
                 ops.guard_queue(self._guard_words, "FrameSequence replay", getattr(self.model, "flow_net", None))
+            if self._guard_words_bw is not None:
+                ops.guard_queue(self._guard_words_bw, "FrameSequence replay (the backward flow)", getattr(self.model, "flow_net", None))
             return self._result

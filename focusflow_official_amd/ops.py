@@ -1218,6 +1218,84 @@ def tracks_advance(pos: Tensor, ids: Tensor, age: Tensor, flow_up: Tensor, left:
     return matches, valid, ids_out, age_out
 
 
+def _fb_field(name: str, t: Tensor, what: str, b: Optional[int], device):
+    """A padded (B,2,Hp,Wp) fp32 flow field of any strides: -> (B, Hp, Wp)."""
+    _require_device(t, name, what, (torch.float32,))
+    if t.dim() != 4 or t.shape[1] != 2 or (b is not None and t.shape[0] != b) or (device is not None and t.device != device):
+        raise _hip.FocusFlowHipError(f"{name}: {what} must be ({'B' if b is None else b},2,Hp,Wp)" + (f" on {device}" if device is not None else "")
+                                     + f", got {tuple(t.shape)} on {t.device}")
+    return t.shape[0], t.shape[2], t.shape[3]
+
+
+def fb_dense(fw: Tensor, bw: Tensor, left: int, top: int, h: int, w: int, alpha: float = 0.01, beta: float = 0.5, out=None):
+    """The forward-backward check of every pixel (csrc/fb_check.hip; the definition is in include/focusflow_hip.h).  fw, bw:
+    (B,2,Hp,Wp) fp32, any strides (independent of each other), the padded forward and backward fields whose h x w frame starts
+    at (left, top).  A pixel goes to its target by fw and comes back by bw sampled bilinearly there; it is occluded where the
+    squared round-trip error exceeds alpha (|fw|^2 + |bw|^2) + beta, or the target lies outside the frame.  -> (err2 (B,1,h,w)
+    fp32, +inf outside the frame; occluded (B,1,h,w) uint8, 1 or 0); out: that tuple to write into (default: new tensors).
+    Exact.  Enqueues only, so it can be captured."""
+    name = "fb_dense"
+    b, hp, wp = _fb_field(name, fw, "fw", None, None)
+    _fb_field(name, bw, "bw", b, fw.device)
+    if tuple(bw.shape[2:]) != (hp, wp):
+        raise _hip.FocusFlowHipError(f"{name}: bw must be ({b},2,{hp},{wp}) as fw is, got {tuple(bw.shape)}")
+    err2, occluded = _track_outs(name, out, (("err2", (b, 1, int(h), int(w)), torch.float32), ("occluded", (b, 1, int(h), int(w)), torch.uint8)), fw.device)
+    _hip.call("ff_fb_dense", _p(fw), fw.stride(0), fw.stride(1), fw.stride(2), fw.stride(3), _p(bw), bw.stride(0), bw.stride(1), bw.stride(2), bw.stride(3),
+              b, int(left), int(top), int(h), int(w), hp, wp, float(alpha), float(beta), _p(err2), _p(occluded), _stream())
+    return err2, occluded
+
+
+def fb_matches(matches: Tensor, valid: Tensor, bw: Tensor, left: int, top: int, h: int, w: int, alpha: float = 0.01, beta: float = 0.5,
+               table=None, out=None):
+    """The forward-backward check of the rows of a matches / valid pair (csrc/fb_check.hip; the definition is in
+    include/focusflow_hip.h).  matches (B,N,4) fp32 [x, y, x', y'] and valid (B,N) uint8 as keypoint_matches or tracks_advance
+    gave them; bw (B,2,Hp,Wp) fp32, any strides, the padded backward field whose h x w frame starts at (left, top).  `valid` is
+    updated in place: cleared where the round trip is inconsistent.  table: None, or (pos, ids, age) of a track table whose
+    slots are the rows: the slot of an inconsistent row dies, every other slot is left alone.  -> (err2 (B,N) fp32: -1 for no
+    row, +inf where the target left the frame; status (B,N) uint8: 0 no row, 1 consistent, 2 the target left the frame, 3
+    inconsistent); out: that tuple to write into (default: new tensors).  Exact.  Enqueues only, so it can be captured."""
+    name = "fb_matches"
+    _require_device(matches, name, "matches", (torch.float32,))
+    _require_device(valid, name, "valid", (torch.uint8,))
+    if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: matches must be contiguous (B,N,4), got {tuple(matches.shape)} strides {matches.stride()}")
+    b, n, _ = matches.shape
+    if tuple(valid.shape) != (b, n) or not valid.is_contiguous() or valid.device != matches.device:
+        raise _hip.FocusFlowHipError(f"{name}: valid must be contiguous {(b, n)} on {matches.device}, got {tuple(valid.shape)} strides {valid.stride()} "
+                                     f"on {valid.device}")
+    _, hp, wp = _fb_field(name, bw, "bw", b, matches.device)
+    pos = ids = age = None
+    if table is not None:
+        if not isinstance(table, (tuple, list)) or len(table) != 3 or any(t is None for t in table):
+            raise _hip.FocusFlowHipError(f"{name}: table must be the tuple (pos, ids, age) of a track table, all three, or None")
+        pos, ids, age = table
+        if _track_table(name, pos, ids, age) != (b, n) or pos.device != matches.device:
+            raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {matches.device}, got pos {tuple(pos.shape)} on {pos.device}")
+    err2, status = _track_outs(name, out, (("err2", (b, n), torch.float32), ("status", (b, n), torch.uint8)), matches.device)
+    _hip.call("ff_fb_matches", _p(matches), _p(valid), n, _p(bw), bw.stride(0), bw.stride(1), bw.stride(2), bw.stride(3), b, int(left), int(top), int(h),
+              int(w), hp, wp, float(alpha), float(beta), _p(pos), _p(ids), _p(age), _p(err2), _p(status), _stream())
+    return err2, status
+
+
+_minus_one = {}      # device -> the one-element tensor -1.0 that negate() scales by
+
+
+def negate(src: Tensor, out: Tensor) -> Tensor:
+    """out = -src for two contiguous fp32 tensors of one shape: ff_scale_add_fwd with the scale -1 and no addend (sign flips are
+    exact; a zero comes out as +0).  One launch, enqueues only."""
+    _require_device(src, "negate", "src", (torch.float32,))
+    _require_device(out, "negate", "out", (torch.float32,))
+    if out.shape != src.shape or not src.is_contiguous() or not out.is_contiguous() or out.device != src.device:
+        raise _hip.FocusFlowHipError(f"negate: src and out must be contiguous and of one shape on one device, got {tuple(src.shape)} and {tuple(out.shape)}")
+    key = src.device
+    minus = _minus_one.get(key)
+    if minus is None:      # (made once per device, outside any capture: FrameSequence asks for it when it allocates)
+        minus = _minus_one[key] = torch.full((1,), -1.0, dtype=torch.float32, device=src.device)
+    # mode 1 with B = 1, C = 1: every element is a "pixel" of the one channel whose scale is s[0]
+    _hip.call("ff_scale_add_fwd", _p(src), 1, _p(minus), 0, None, None, 0, _p(out), 1, 1, 1, src.numel(), 1, _stream())
+    return out
+
+
 def coords_step(coords1: Tensor, delta: Optional[Tensor], flow4: Optional[Tensor], slot: Optional[Tensor]):
     b, h, w, _ = coords1.shape
     _hip.call("ff_coords_step", _p(coords1), _p(delta), _ld(delta) if delta is not None else 0, _p(flow4), _p(slot),

@@ -66,7 +66,9 @@ const char* ff_last_error(void);
  *                missing one and asks for a rebuild)
  *   7 (unchanged): entry points only: ff_tracks_replenish, ff_tracks_mask, ff_tracks_advance (key-point tracks with
  *                persistent ids across the frames of a video session)
- *   7 (unchanged): entry point only: ff_encoder_tail_fwd (FFEncoderTail: the encoders' output stage as one launch) */
+ *   7 (unchanged): entry point only: ff_encoder_tail_fwd (FFEncoderTail: the encoders' output stage as one launch)
+ *   7 (unchanged): entry points only: ff_fb_dense, ff_fb_matches (forward-backward consistency of a video session: the
+ *                occlusion map, and tracks culled by their round-trip error) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -459,6 +461,50 @@ int ff_tracks_mask(const float* pos, const long long* ids, int N, int B, int H, 
 int ff_tracks_advance(float* pos, long long* ids, int* age, int N, const float* flow_up, long long ld_b, long long ld_c,
                       long long ld_row, long long ld_col, int B, int left, int top, int H, int W, int Hp, int Wp, float* matches,
                       unsigned char* valid, long long* ids_out, int* age_out, void* stream);
+/* Forward-backward consistency: a start point goes to its target by the forward flow, comes back by the backward flow sampled
+ * at the target, and is INCONSISTENT (occluded, or on a bad vector) where the round trip ends too far from where it began:
+ * the occlusion criterion of UnFlow (Meister et al. 2018; its defaults are alpha = 0.01, beta = 0.5).  fw and bw are padded
+ * (B,2,Hp,Wp) fields addressed by element strides with the frame at (left, top), exactly as ff_tracks_advance addresses
+ * flow_up; their strides are independent.  All arithmetic is fp32, every operation rounded separately, nothing contracted to an
+ * FMA.  bilinear(bw, x', y') is ff_tracks_advance's blend, word for word: x0 = (int) floorf(x') clamped to 0 .. W - 1,
+ * x1 = min(x0 + 1, W - 1), fx = x' - (float) x0, the same for y; wx0 = 1 - fx; top = wx0 f00 + fx f01; bot = wx0 f10 + fx f11;
+ * wy0 = 1 - fy; value = wy0 top + fy bot; the taps never leave the H x W frame.  For a start point (X, Y) and its forward
+ * target (x', y'):
+ *   inside = 0 <= x' <= W - 1 and 0 <= y' <= H - 1                        (a NaN gives false)
+ *   if not inside:  err2 = +inf, inconsistent                              (bw is not read)
+ *   else:
+ *     (ub, vb) = bilinear(bw, x', y')
+ *     du = (x' + ub) - X;  dv = (y' + vb) - Y;  err2 = du du + dv dv       where the round trip ends, against where it began
+ *     fu = x' - X;  fv = y' - Y;  mf = fu fu + fv fv;  mb = ub ub + vb vb
+ *     bound = alpha (mf + mb) + beta
+ *     inconsistent = not (err2 <= bound)                                   (a NaN anywhere gives inconsistent)
+ * err2 is the squared round-trip error in px^2: kept squared, the result needs no sqrt and stays exact (tests/fb_ref.py
+ * restates all of this in numpy; the tests ask for equality).
+ *
+ * ff_fb_dense: every pixel (x, y) of the H x W frame is a start point: X = (float) x, Y = (float) y,
+ * x' = X + fw(b, 0, y + top, x + left), y' = Y + fw(b, 1, ...): the adds of ff_keypoint_matches.  err2 (B,1,H,W) fp32 and
+ * occluded (B,1,H,W) uint8 (1: inconsistent, 0: consistent), both contiguous.  One launch.
+ *
+ * ff_fb_matches: the start points are the rows of a matches (B,N,4) [x, y, x', y'] / valid (B,N) pair as ff_keypoint_matches or
+ * ff_tracks_advance wrote them, 1 <= N <= 4096; X, Y, x', y' are taken from the row.  A row's prior state is read from the
+ * row itself: x < 0 (a no-row holds -1) is no row; otherwise valid = 0 on entry means the target left the frame.
+ *   status (B,N) uint8: 0 = no row (a dead slot, beyond the count, a point outside the frame); 1 = consistent; 2 = the target
+ *                       left the frame (valid was 0 on entry); 3 = inconsistent
+ *   err2 (B,N) fp32:    -1 for status 0, +inf for status 2, otherwise the round trip's
+ * valid is updated in place: 1 where the status is 1, else 0.  pos, ids, age: an optional track table (B,N,..) as above, all
+ * three or all three null; a slot whose row gets status 3 dies (ids = -1, pos = -1, age = 0), every other slot is left alone.
+ * Since the dense adds are ff_keypoint_matches', a row at an integer position has the err2 and the verdict of ff_fb_dense at
+ * that pixel, as values.  matches 16-byte aligned, pos 8-byte aligned.  One launch, one thread per row.
+ *
+ * Both enqueue only (capturable), allocate nothing and use no atomics.  Refused (FF_EINVAL): a null pointer (but for the
+ * table), a partial table, N outside 1 .. 4096, B, H or W < 1, H or W > 2^24, left or top < 0, left + W > Wp, top + H > Hp,
+ * alpha or beta negative or NaN. */
+int ff_fb_dense(const float* fw, long long fw_ld_b, long long fw_ld_c, long long fw_ld_row, long long fw_ld_col, const float* bw,
+                long long bw_ld_b, long long bw_ld_c, long long bw_ld_row, long long bw_ld_col, int B, int left, int top, int H, int W,
+                int Hp, int Wp, float alpha, float beta, float* err2, unsigned char* occluded, void* stream);
+int ff_fb_matches(const float* matches, unsigned char* valid, int N, const float* bw, long long bw_ld_b, long long bw_ld_c,
+                  long long bw_ld_row, long long bw_ld_col, int B, int left, int top, int H, int W, int Hp, int Wp, float alpha,
+                  float beta, float* pos, long long* ids, int* age, float* err2, unsigned char* status, void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
