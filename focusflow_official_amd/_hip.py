@@ -128,6 +128,8 @@ _SIGS = {
                     _fp, _fp, _fp],
     "ff_fb_matches": [_fp, _fp, C.c_int, _fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                       _fp, _fp, _fp, _fp, _fp, _fp],
+    "ff_epipolar_ransac": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint, _fp, C.c_int, _fp, _fp, _fp, _fp,
+                           _fp, _fp, _fp, _fp, _fp, _fp, _ll, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],
@@ -192,7 +194,7 @@ _SIGS = {
                          C.c_int, _fp],
 }
 EXPORTS = sorted(list(_SIGS) + ["ff_last_error", "ff_abi_version", "ff_corr_plane_elems", "ff_conv2d_splitk_hint", "ff_conv2d_stats_parts", "ff_fusion_pair_tile",
-                                 "ff_forward_interpolate_ws", "ff_good_features_ws"])
+                                 "ff_forward_interpolate_ws", "ff_good_features_ws", "ff_epipolar_ws"])
 
 ABI_VERSION = 7      # include/focusflow_hip.h: FF_ABI_VERSION
 _lib = None
@@ -250,6 +252,8 @@ def load():
     lib.ff_forward_interpolate_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_good_features_ws.restype = C.c_int
     lib.ff_good_features_ws.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.ff_epipolar_ws.restype = C.c_int
+    lib.ff_epipolar_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_conv2d_stats_parts.restype = C.c_int
     lib.ff_conv2d_stats_parts.argtypes = [C.POINTER(FFConvParams)]
     got = lib.ff_abi_version()

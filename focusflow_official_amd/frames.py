@@ -32,12 +32,25 @@ forward flow to it (csrc/fb_check.hip): a point whose round trip does not end wh
     res.fb.point_err2, res.fb.status         # per row of res.matches: (B,N) fp32, (B,N) uint8 (0 no row, 1 consistent, 2 the target
                                              # left the frame, 3 inconsistent); res.valid is 1 only where the status is 1, and
                                              # with tracks the slots of status 3 have died: the next replenish refills them
+
+With epipolar=True (or epipolar=geometry.Epipolar(threshold, hypotheses, min_inliers, min_ratio, cull, seed)) the step ends with the
+epipolar check (csrc/epipolar.hip): a RANSAC fundamental matrix over the rows that are still valid, so behind fb= over the
+round-trip-consistent ones.
+
+    seq = FrameSequence(model, raft_iters=12, keypoints=GoodFeatures(), tracks=True, fb=True, epipolar=True)
+    res = seq.push(frame)
+    res.epi.F, res.epi.ok                    # (B,3,3) fp32 in pixel coordinates of the frame, x'^t F x = 0; (B) uint8: a verdict
+    res.epi.status, res.epi.dist2            # per row of res.matches: (B,N) uint8 (0 no row, 1 inlier, 2 not a candidate, 3
+                                             # outlier, 4 no verdict), (B,N) fp32 Sampson distance in px^2; where there is a
+                                             # verdict res.valid is cleared for the outliers, and with tracks their slots have died
+    res.epi.inliers, res.epi.candidates      # (B) int32
 """
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import ops
+from .geometry import EpiResult, EpipolarCheck, as_epipolar
 from .model import FF_RAFT_FUSION
 from .tracks import MAX_SLOTS, TrackResult, TrackTable
 
@@ -68,20 +81,18 @@ class FrameResult(tuple):
     """(flow_low, flow_up, matches, valid, count): the named tuple a push returns.  In tracks mode it is a TrackedFrameResult, the
     same with a sixth item `tracks` (a tracks.TrackResult); in a session with fb= it carries a trailing item `fb` (an FBResult)
     behind those: a CheckedFrameResult (six items) or a TrackedCheckedFrameResult (seven).  Without either the tuple has the five
-    items it always had, so a caller that unpacks or walks them goes on working, and `.tracks` and `.fb` are None.  All four
-    behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
+    items it always had, so a caller that unpacks or walks them goes on working, and `.tracks` and `.fb` are None.  A session with
+    epipolar= gets the shape it would have without, plus a last item `epi` (a geometry.EpiResult): Epi-, TrackedEpi-, CheckedEpi-
+    and TrackedCheckedEpiFrameResult; `.epi` is None in the four shapes without.  All eight behave as typing.NamedTuple classes do:
+    `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
     __slots__ = ()
     _fields = ("flow_low", "flow_up", "matches", "valid", "count")
 
-    def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None, fb: Optional[FBResult] = None):
-        items = (flow_low, flow_up, matches, valid, count)
-        if tracks is None and fb is None:
-            return tuple.__new__(FrameResult, items)
-        if fb is None:
-            return tuple.__new__(TrackedFrameResult, items + (tracks,))
-        if tracks is None:
-            return tuple.__new__(CheckedFrameResult, items + (fb,))
-        return tuple.__new__(TrackedCheckedFrameResult, items + (tracks, fb))
+    def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None, fb: Optional[FBResult] = None,
+                epi: Optional[EpiResult] = None):
+        extras = tuple(x for x in (tracks, fb, epi) if x is not None)
+        shape = _SHAPES[(tracks is not None, fb is not None, epi is not None)]
+        return tuple.__new__(shape, (flow_low, flow_up, matches, valid, count) + extras)
 
     flow_low = property(lambda self: self[0])
     flow_up = property(lambda self: self[1])
@@ -90,23 +101,31 @@ class FrameResult(tuple):
     count = property(lambda self: self[4])
     tracks = property(lambda self: None)
     fb = property(lambda self: None)
+    epi = property(lambda self: None)
 
     def __getnewargs__(self):      # (copy, deepcopy and pickle rebuild through __new__, item by item)
-        return tuple(self[:5]) + (self.tracks, self.fb)
+        return tuple(self[:5]) + (self.tracks, self.fb, self.epi)
 
     @classmethod
     def _make(cls, iterable):
-        """From the items of any of the four shapes; a sixth item is `fb` if it is an FBResult, else `tracks`."""
+        """From the items of any of the eight shapes; an item behind the fifth is `fb` if it is an FBResult, `epi` if it is an
+        EpiResult, else `tracks`."""
         items = tuple(iterable)
-        if len(items) == 6 and isinstance(items[5], FBResult):
-            return FrameResult(*items[:5], fb=items[5])
-        return FrameResult(*items)
+        if len(items) <= 5 or len(items) > 8:
+            return FrameResult(*items)      # (too few or too many: the TypeError of __new__)
+        extras = {}
+        for x in items[5:]:
+            name = "fb" if isinstance(x, FBResult) else "epi" if isinstance(x, EpiResult) else "tracks"
+            if name in extras:
+                raise TypeError(f"FrameResult._make: two items for `{name}`")
+            extras[name] = x
+        return FrameResult(*items[:5], **extras)
 
     def _asdict(self):
         return dict(zip(self._fields, self))
 
     def _replace(self, **kwargs):
-        unknown = set(kwargs) - set(TrackedCheckedFrameResult._fields)
+        unknown = set(kwargs) - set(TrackedCheckedEpiFrameResult._fields)
         if unknown:
             raise ValueError(f"Got unexpected field names: {sorted(unknown)!r}")
         return FrameResult(**{**self._asdict(), **kwargs})
@@ -135,6 +154,44 @@ class TrackedCheckedFrameResult(FrameResult):
     _fields = FrameResult._fields + ("tracks", "fb")
     tracks = property(lambda self: self[5])
     fb = property(lambda self: self[6])
+
+
+class EpiFrameResult(FrameResult):
+    """A FrameResult of a session with epipolar=, without tracks and fb=: six items, the last one `epi`.  Made by FrameResult(..., epi=...)."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("epi",)
+    epi = property(lambda self: self[5])
+
+
+class TrackedEpiFrameResult(FrameResult):
+    """A FrameResult of a session with tracks and epipolar=: seven items, `tracks` and `epi` last."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("tracks", "epi")
+    tracks = property(lambda self: self[5])
+    epi = property(lambda self: self[6])
+
+
+class CheckedEpiFrameResult(FrameResult):
+    """A FrameResult of a session with fb= and epipolar=, without tracks: seven items, `fb` and `epi` last."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("fb", "epi")
+    fb = property(lambda self: self[5])
+    epi = property(lambda self: self[6])
+
+
+class TrackedCheckedEpiFrameResult(FrameResult):
+    """A FrameResult of a session with tracks, fb= and epipolar=: eight items, `tracks`, `fb` and `epi` last."""
+    __slots__ = ()
+    _fields = FrameResult._fields + ("tracks", "fb", "epi")
+    tracks = property(lambda self: self[5])
+    fb = property(lambda self: self[6])
+    epi = property(lambda self: self[7])
+
+
+# (tracks, fb, epi) present -> the shape
+_SHAPES = {(False, False, False): FrameResult, (True, False, False): TrackedFrameResult, (False, True, False): CheckedFrameResult,
+           (True, True, False): TrackedCheckedFrameResult, (False, False, True): EpiFrameResult, (True, False, True): TrackedEpiFrameResult,
+           (False, True, True): CheckedEpiFrameResult, (True, True, True): TrackedCheckedEpiFrameResult}
 
 
 class FrameSequence:
@@ -179,12 +236,20 @@ class FrameSequence:
     inconsistent and, with tracks, kills those slots: the table the next pair starts from is the culled one, and the next
     replenish refills what the check freed.  The result then carries a trailing `fb` (an FBResult).
 
+    epipolar=True or epipolar=geometry.Epipolar(...) (needs keypoints=): the step ends with ops.epipolar_ransac on the pair's
+    matches / valid, behind the advance (or the matches) and behind the forward-backward check when fb= is set, so its candidates
+    are the rows that are still valid.  Where a pair gets a verdict it clears `valid` for the outliers and, with tracks (and
+    Epipolar.cull), kills their slots: the table the next pair starts from is the culled one.  The draws follow an epoch word on
+    the device that every step increments - a replay draws anew -; reset() leaves it alone, a new shape starts it at 0 with the
+    other buffers.  The result then carries `epi` (a geometry.EpiResult) as its last item.  F is neither forced to rank 2 nor
+    refitted: see geometry.
+
     The tensors of a result are the session's static buffers: valid until the next push.  A frame in pinned host memory is
     read by an asynchronous copy: leave it alone until work enqueued after the push has finished (the event a consumer
     waits for anyway before it reads the matches)."""
 
     def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel",
-                 tracks=None, fb=None):
+                 tracks=None, fb=None, epipolar=None):
         if not isinstance(model, FF_RAFT_FUSION):
             raise ValueError(f"model: FrameSequence drives FF_RAFT_FUSION, whose forward takes flow_init; {type(model).__name__} "
                              "(FF_PWCNET has no flow_init) runs pair by pair through graph.GraphedForward")
@@ -210,6 +275,9 @@ class FrameSequence:
                 raise ValueError(f"fb: alpha={self.fb.alpha}, beta={self.fb.beta}: both >= 0 (and no NaN)")
             if self.fb.iters is not None and int(self.fb.iters) < 1:
                 raise ValueError(f"fb: iters={self.fb.iters}: None (the session's raft_iters) or at least 1")
+        self.epipolar = as_epipolar(epipolar)      # the geometry.Epipolar of the session; None: no epipolar check
+        if self.epipolar is not None and keypoints is None:
+            raise ValueError("epipolar: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
         self._reads_mask = getattr(model, "mask_modal", None) is not None
         self._require_eval()
         self._key = None
@@ -224,6 +292,7 @@ class FrameSequence:
         self._u8 = self._mask_in = self._img1 = self._img2 = self._mask1 = self._mask_next = self._mask_det = self._flow_init = None
         self._table = None
         self._fb_mask = self._fb_mask_det = self._fb_init = self._guard_words_bw = None
+        self._epi = None      # the geometry.EpipolarCheck: workspace, outputs, the epoch word
         self._frames = 0      # frames of the running sequence that have been ingested
 
     @property
@@ -324,6 +393,9 @@ class FrameSequence:
             if self.fb.warm:
                 self._fb_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
                 ops.negate(self._fb_init, self._fb_init)      # (makes the constant negate() reads now, not inside a capture)
+        if self.epipolar is not None:
+            self._epi = EpipolarCheck(self.epipolar)
+            self._epi.prepare(b, self._slots or self.keypoints.max_corners, device)      # (now, not inside a capture)
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -360,7 +432,10 @@ class FrameSequence:
         elif det is not None:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
         fb = self._check(flow_low, flow_up, matches, valid) if self.fb is not None else None
-        return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, count, tracks, fb)
+        epi = None
+        if self._epi is not None:      # last: its candidates are the rows that are still valid
+            epi = self._epi(matches, valid, h, w, table=None if tb is None else (tb.pos, tb.ids, tb.age))
+        return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, count, tracks, fb, epi)
 
     def _check(self, flow_low, flow_up, matches, valid):
         """The forward-backward part of a step, behind the advance / the matches: the backward pair's mask, the backward flow's
@@ -406,7 +481,8 @@ class FrameSequence:
         """graph.GraphedForward's capture around `_step`: warm-up steps on a side stream (they pack weights, set kernel
         attributes, decide the routes and warm the allocator), what they changed put back, then the capture with static
         guard words."""
-        keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init) if t is not None]
+        epoch = self._epi.epoch if self._epi is not None else None      # (the warm-up steps would spend epochs: graph and eager draw alike)
+        keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init, epoch) if t is not None]
         table = self._table.state() if self._table is not None else None      # (the warm-up steps would move tracks and spend ids)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())

@@ -1277,6 +1277,59 @@ def fb_matches(matches: Tensor, valid: Tensor, bw: Tensor, left: int, top: int, 
     return err2, status
 
 
+def epipolar_ws(b: int, n: int, hypotheses: int) -> int:
+    """Bytes of workspace ff_epipolar_ransac needs for (B, N, K); 0: the shape is not supported."""
+    return _hip.load().ff_epipolar_ws(int(b), int(n), int(hypotheses))
+
+
+def epipolar_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: float, hypotheses: int, min_inliers: int, permille: int, seed: int,
+                    epoch: Tensor, table=None, cull: bool = True, out=None, ws: Optional[Tensor] = None):
+    """The epipolar check of the rows of a matches / valid pair (csrc/epipolar.hip; the definition is in include/focusflow_hip.h):
+    a RANSAC over `hypotheses` 8-point fundamental matrices in coordinates normalised by the h x w frame, scored by the Sampson
+    distance against `threshold` px.  matches (B,N,4) fp32 [x, y, x', y'] and valid (B,N) uint8 as keypoint_matches,
+    tracks_advance or fb_matches left them; the candidates are the rows with valid = 1.  There is a verdict where at least 8
+    candidates exist and the best model has at least min_inliers inliers and permille / 1000 of the candidates; then `valid` is
+    cleared in place where a candidate is an outlier, and with cull and a table (pos, ids, age) whose slots are the rows those
+    slots die.  epoch: one int32 on the device, read by the draws and incremented by the call.  -> (F (B,3,3) fp32 in pixel
+    coordinates, x'^t F x = 0, zeros without a verdict; inliers (B) int32; candidates (B) int32; ok (B) uint8; status (B,N) uint8:
+    0 no row, 1 inlier, 2 not a candidate, 3 outlier, 4 candidate but no verdict; dist2 (B,N) fp32 px^2: -1 no row, +inf without a
+    verdict); out: that tuple to write into (default: new tensors).  ws: a uint8 device tensor of epipolar_ws(B, N, hypotheses)
+    bytes to work in (default: a new one per call).  Exact.  Enqueues only, so it can be captured."""
+    name = "epipolar_ransac"
+    _require_device(matches, name, "matches", (torch.float32,))
+    _require_device(valid, name, "valid", (torch.uint8,))
+    if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: matches must be contiguous (B,N,4), got {tuple(matches.shape)} strides {matches.stride()}")
+    b, n, _ = matches.shape
+    dev = matches.device
+    if tuple(valid.shape) != (b, n) or not valid.is_contiguous() or valid.device != dev:
+        raise _hip.FocusFlowHipError(f"{name}: valid must be contiguous {(b, n)} on {dev}, got {tuple(valid.shape)} strides {valid.stride()} on {valid.device}")
+    _require_device(epoch, name, "epoch", (torch.int32,))
+    if epoch.numel() != 1 or epoch.device != dev:
+        raise _hip.FocusFlowHipError(f"{name}: epoch must be one int32 on {dev}, got {tuple(epoch.shape)} on {epoch.device}")
+    pos = ids = age = None
+    if table is not None:
+        if not isinstance(table, (tuple, list)) or len(table) != 3 or any(t is None for t in table):
+            raise _hip.FocusFlowHipError(f"{name}: table must be the tuple (pos, ids, age) of a track table, all three, or None")
+        pos, ids, age = table
+        if _track_table(name, pos, ids, age) != (b, n) or pos.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {dev}, got pos {tuple(pos.shape)} on {pos.device}")
+    F, inliers, candidates, ok, status, dist2 = _track_outs(name, out, (("F", (b, 3, 3), torch.float32), ("inliers", (b,), torch.int32),
+                                                                        ("candidates", (b,), torch.int32), ("ok", (b,), torch.uint8),
+                                                                        ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
+    nbytes = epipolar_ws(b, n, hypotheses)
+    if ws is None:
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # (an unsupported shape is refused by the call itself, with its reason)
+    else:
+        _require_device(ws, name, "ws", (torch.uint8,))
+        if ws.numel() < nbytes or not ws.is_contiguous() or ws.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, got {ws.numel()} on {ws.device}")
+    _hip.call("ff_epipolar_ransac", _p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), int(permille),
+              int(seed) & 0xffffffff, _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(F), _p(dist2), _p(status), _p(inliers), _p(candidates),
+              _p(ok), _p(ws), ws.numel(), _stream())
+    return F, inliers, candidates, ok, status, dist2
+
+
 _minus_one = {}      # device -> the one-element tensor -1.0 that negate() scales by
 
 

@@ -68,7 +68,9 @@ const char* ff_last_error(void);
  *                persistent ids across the frames of a video session)
  *   7 (unchanged): entry point only: ff_encoder_tail_fwd (FFEncoderTail: the encoders' output stage as one launch)
  *   7 (unchanged): entry points only: ff_fb_dense, ff_fb_matches (forward-backward consistency of a video session: the
- *                occlusion map, and tracks culled by their round-trip error) */
+ *                occlusion map, and tracks culled by their round-trip error)
+ *   7 (unchanged): entry points only: ff_epipolar_ws, ff_epipolar_ransac (epipolar check of a video session: a RANSAC
+ *                fundamental matrix per pair, and tracks culled as its outliers) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -505,6 +507,47 @@ int ff_fb_dense(const float* fw, long long fw_ld_b, long long fw_ld_c, long long
 int ff_fb_matches(const float* matches, unsigned char* valid, int N, const float* bw, long long bw_ld_b, long long bw_ld_c,
                   long long bw_ld_row, long long bw_ld_col, int B, int left, int top, int H, int W, int Hp, int Wp, float alpha,
                   float beta, float* pos, long long* ids, int* age, float* err2, unsigned char* status, void* stream);
+/* Epipolar check of a video session (csrc/epipolar.hip): do the rows of a matches (B,N,4) [x, y, x', y'] / valid (B,N) pair
+ * agree with ONE rigid camera motion?  A RANSAC (Fischler & Bolles 1981) over K fundamental matrices from 8 rows each, in
+ * frame-normalised coordinates (Hartley 1997), scored by the Sampson distance.  Exact: fp32, every operation rounded
+ * separately, no FMA; tests/epipolar_ref.py restates all of it in numpy and the tests ask for equality.  Per sample b:
+ *   candidates     rows with valid = 1, x >= 0 (a no-row holds -1) and four finite values; M of them, ranked by row index
+ *   normalisation  s = (float)(2 / (H + W)); xn = (x - (W - 1) / 2) s, yn = (y - (H - 1) / 2) s, likewise x', y'
+ *   draws          hypothesis k of epoch e takes 8 distinct ranks by Floyd's algorithm: for j = 0 .. 7, n = M - 8 + j,
+ *                  t = word(seed, e, b, 8 k + j) mod (n + 1), take t unless taken already, else n.  word: with mix = lowbias32
+ *                  (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16) on uint32,
+ *                  word = mix(mix(mix(mix(seed + 0x9e3779b9) ^ e) ^ b) ^ counter)
+ *   model          the 8 x 9 system with rows [x'x, x'y, x', y'x, y'y, y', x, y, 1], eliminated with full pivoting (the entry
+ *                  of largest magnitude of the remaining block under a strict > from 0, the first one in (row, column) order;
+ *                  row r -= (A(r,p) / A(p,p)) row p, the product and the difference rounded separately, correctly rounded
+ *                  division), back-substituted with the free unknown 1 (acc = A(i,8), += A(i,c) z(c) for c = i + 1 .. 7,
+ *                  z(i) = -acc / A(i,i)).  A hypothesis that meets no pivot > 0 in some step, or whose f is not finite, is
+ *                  degenerate and scores 0.  No rank-2 enforcement, no refit on the inliers: both are the consumer's, who has
+ *                  the calibration
+ *   score          Fx = F (x, y, 1), Ftx = F^t (x', y', 1), each (a x + b y) + c; e = (x' Fx0 + y' Fx1) + Fx2; num = e e;
+ *                  den = ((Fx0^2 + Fx1^2) + Ftx0^2) + Ftx1^2; a row is an inlier where num <= t den, t = (float)(threshold^2 s^2)
+ *                  made in double.  The best hypothesis has the most inliers, the lowest k among equal counts
+ *   verdict        ok = M >= 8 and count >= min_inliers and 1000 count >= permille M
+ * Outputs: F (B,3,3) in pixel coordinates of the unpadded frame, x'^t F x = 0: T^t Fn T with T = [[s, 0, -cx s], [0, s, -cy s],
+ * [0, 0, 1]], G = Fn T first (G(i,0) = f(i,0) s, G(i,1) = f(i,1) s, G(i,2) = f(i,2) - (G(i,0) cx + G(i,1) cy)), then T^t G the
+ * same way down the columns; zeros when ok = 0.  dist2 (B,N): the Sampson distance in px^2 under the best F, (num / den) / s^2
+ * (den = 0: 0 for an inlier, else +inf), -1 for no row, +inf for a row with a non-finite value and for every row when ok = 0.
+ * status (B,N) uint8: 0 no row, 1 inlier, 2 not a candidate, 3 outlier, 4 candidate but no verdict.  inliers (B) int32 (0 when
+ * ok = 0: the number of rows of status 1), candidates (B) int32, ok (B) uint8.  Side effects, only where ok = 1: valid is
+ * cleared where the status is 3, and with cull != 0 and a table (pos, ids, age: all three or none) those slots die as in
+ * ff_fb_matches.  epoch: one device int32, read by the draws and incremented by one at the end of every call, so that a
+ * captured call draws anew at every replay.  A stationary camera makes every skew-symmetric F fit: everything is an inlier
+ * then, which is harmless.  ws: ff_epipolar_ws bytes (ws_size says how many there are), 16-byte aligned, contents need no
+ * initialisation.  Four launches; enqueues only (capturable), allocates nothing, no atomics.
+ * Refused (FF_EINVAL): N outside 1 .. 4096, K outside 1 .. 4096, B outside 1 .. 1024, H or W outside 1 .. 2^24, threshold
+ * negative, infinite or NaN, min_inliers < 1, permille outside 0 .. 1000, a null pointer (but for the table), a partial table,
+ * matches not 16-byte or pos not 8-byte aligned, a ws that is too small.
+ *   ff_epipolar_ws   bytes of workspace for (B, N, K); 0 = shape not supported.  A plain return value, not a status. */
+int ff_epipolar_ws(int B, int N, int K);
+int ff_epipolar_ransac(const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K, int min_inliers,
+                       int permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids, int* age, float* F,
+                       float* dist2, unsigned char* status, int* inliers, int* candidates, unsigned char* ok, void* ws,
+                       long long ws_size, void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
