@@ -39,6 +39,16 @@ class FFEncoderTail(C.Structure):
     ]
 
 
+class FFConvS2Pair(C.Structure):
+    """include/focusflow_hip.h: FFConvS2Pair (ff_conv_s2_pair_fwd)."""
+    _fields_ = [
+        ("x", _fp), ("x_ld", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+        ("k", C.c_int * 2), ("stride", C.c_int * 2), ("pad", C.c_int * 2), ("w3_frag", _fp), ("w1_frag", _fp), ("w_format", C.c_int),
+        ("bias", _fp * 2), ("scale", _fp * 2), ("shift", _fp * 2), ("act", C.c_int * 2), ("y", _fp * 2), ("y_ld", C.c_int * 2),
+        ("stats_part", _fp * 2),
+    ]
+
+
 class FFConvParams(C.Structure):
     _fields_ = [
         ("x", _fp * MAX_SEG), ("x_ld", C.c_int * MAX_SEG), ("x_c", C.c_int * MAX_SEG),
@@ -137,6 +147,7 @@ _SIGS = {
                         _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_fusion_pair_fwd": [C.POINTER(FFFusionPair), _fp],
     "ff_encoder_tail_fwd": [C.POINTER(FFEncoderTail), _fp],
+    "ff_conv_s2_pair_fwd": [C.POINTER(FFConvS2Pair), _fp],
     "ff_gru_rh": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _ll, C.c_int, _fp],
     "ff_gru_blend": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _ll, C.c_int, _fp],
     "ff_upsample_flow": [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp],
@@ -194,7 +205,7 @@ _SIGS = {
                          C.c_int, _fp],
 }
 EXPORTS = sorted(list(_SIGS) + ["ff_last_error", "ff_abi_version", "ff_corr_plane_elems", "ff_conv2d_splitk_hint", "ff_conv2d_stats_parts", "ff_fusion_pair_tile",
-                                 "ff_forward_interpolate_ws", "ff_good_features_ws", "ff_epipolar_ws"])
+                                 "ff_forward_interpolate_ws", "ff_good_features_ws", "ff_epipolar_ws", "ff_conv_s2_pair_stats_parts"])
 
 ABI_VERSION = 7      # include/focusflow_hip.h: FF_ABI_VERSION
 _lib = None
@@ -256,6 +267,8 @@ def load():
     lib.ff_epipolar_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_conv2d_stats_parts.restype = C.c_int
     lib.ff_conv2d_stats_parts.argtypes = [C.POINTER(FFConvParams)]
+    lib.ff_conv_s2_pair_stats_parts.restype = C.c_int
+    lib.ff_conv_s2_pair_stats_parts.argtypes = [C.c_int, C.c_int]
     got = lib.ff_abi_version()
     if got != ABI_VERSION:
         raise FocusFlowHipError(f"{LIB_PATH} speaks ABI version {got}, these bindings (FFConvParams layout, argument lists) "

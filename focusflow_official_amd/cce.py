@@ -393,7 +393,8 @@ def _branch_stream(device):
 _FUSION_PAIR = os.environ.get("FF_FUSION_PAIR", "1") != "0"   # fusion units 1-3 as ff_fusion_pair_fwd launches with lazy normalised inputs (inference; A/B switch)
 _PAIR_FUSION = True       # both 1x1 convs of a fusion unit in one launch where ff_fusion_pair_fwd has no instance (inference)
 _ENCODER_TAIL = True      # fusion4, conv2 / mask_conv2 and fusion5 as ONE launch with a composed weight (csrc/encoder_tail.hip; inference)
-_W_LIMIT = 4094.0         # |w| of a packed split row stays below this (csrc/ff_common.h)
+_S2_PAIR = True           # conv1 and the 1x1 shortcut of a stride-2 block entry as ONE launch (csrc/conv_s2_pair.hip; inference)
+_W_LIMIT = 4094.0        # |w| of a packed split row stays below this (csrc/ff_common.h)
 
 
 def invalidate_packed(module: nn.Module) -> int:
@@ -660,15 +661,46 @@ class _ResidualEncoder(nn.Module):
         """Both convolutions of the block and its two norms go through the tape, with x itself differentiated."""
         return torch.is_grad_enabled() and x.requires_grad and self.norm_fn in ("instance", "batch")
 
+    def _s2_pair(self, blk: ResidualBlock, x):
+        """The entry of a stride-2 block - conv1 and the shortcut's 1x1 - as ONE launch (ff_conv_s2_pair_fwd) where it applies:
+        inference, a split weight format, InstanceNorm or eval BatchNorm, the (3, 3, 2, pad 1) + (1, 1, 2, pad 0) pair with equal
+        channels, an input the kernel reads.  -> None (the separate launches), or (t1, stats1, d, stats_d) raw outputs with their
+        statistics (InstanceNorm), or (relu(norm1(conv1 x)), norm3(shortcut x)) with the folded BatchNorms in the epilogue."""
+        p1, pd = blk._p1, blk._pd
+        if not (_S2_PAIR and pd is not None and not torch.is_grad_enabled() and ops.w_format() in (_hip.W_F16X3, _hip.W_F16)):
+            return None
+        if self.norm_fn == "batch":
+            if blk.norm1.training or blk.norm3.training:
+                return None
+        elif self.norm_fn != "instance":
+            return None
+        geom = lambda pc: (pc.kh, pc.kw, pc.stride, pc.pad, pc.dil)        # noqa: E731
+        if (geom(p1) != (3, 3, 2, (1, 1), 1) or geom(pd) != (1, 1, 2, (0, 0), 1) or (p1.cin, p1.cout) != (pd.cin, pd.cout)
+                or p1.cin_pad != p1.cin or pd.cin_pad != pd.cin or p1.force_f32 or pd.force_f32 or not p1.plain or not pd.plain
+                or not ops.conv_s2_pair_inputs_ok(x, p1.cout) or x.shape[3] != p1.cin):
+            return None
+        (_, b3), (_, b1) = p1.get(), pd.get()
+        w3, w1 = p1.frag(), pd.frag()
+        if self.norm_fn == "instance":
+            return ops.conv_s2_pair(x, w3, w1, b3, b1, p1.cout, p1.fmt, want_stats=True)
+        (s3, h3), (s1, h1) = ops.bn_fold(blk.norm1), ops.bn_fold(blk.norm3)
+        return ops.conv_s2_pair(x, w3, w1, b3, b1, p1.cout, p1.fmt, scale=(s3, s1), shift=(h3, h1), act=(ACT_RELU, ACT_NONE))
+
     def _block(self, blk: ResidualBlock, x, lazy_out=False):
         p2 = blk._p2
+        pair = self._s2_pair(blk, x) if blk.downsample is not None else None
         if (_NORM_ON_LOAD and self.norm_fn == "instance" and not torch.is_grad_enabled() and ops.w_format() in (_hip.W_F16X3, _hip.W_F16)
                 and p2.cin % 32 == 0 and (p2.kh, p2.kw, p2.stride) == (3, 3, 1)):
             # inference: conv2 applies relu(norm1(.)) while it loads conv1's raw output - one full read + write of the
             # activation less per block (same coefficients, same arithmetic as ff_norm_apply: bit-identical results)
-            t1, st = blk._p1(x, want_stats=True)
+            if pair is not None:
+                t1, st, d, std = pair
+            else:
+                t1, st = blk._p1(x, want_stats=True)
             sc, sh = ops.norm_coeffs(st, t1.shape[1] * t1.shape[2], EPS)
-            if blk.downsample is not None:
+            if pair is not None:
+                x = ops.norm_apply(d, std, True, EPS, act=ACT_NONE, out=d)
+            elif blk.downsample is not None:
                 x = self._conv_norm(x, blk._pd, blk.norm3, ACT_NONE)
             t2, st2 = p2(t1, in_scale=sc, in_shift=sh, in_act=ACT_RELU, want_stats=True)
             if lazy_out:     # the stage's last block: relu(x + relu(norm2(t2))) is evaluated by the fusion unit's loader
@@ -677,9 +709,16 @@ class _ResidualEncoder(nn.Module):
         # recorded passes, plain blocks (the input is the skip connection): the skip's gradient is added inside conv1's
         # input-gradient launch instead of by an autograd add over two activation-sized tensors
         fuse = blk.downsample is None and self._block_recorded(blk, x) and fn.res_grad_fused(blk._p1)
-        y = self._conv_norm(x, blk._p1, blk.norm1, ACT_RELU, take_res=fuse)
-        if blk.downsample is not None:
-            x = self._conv_norm(x, blk._pd, blk.norm3, ACT_NONE)
+        if pair is not None and self.norm_fn == "instance":
+            t1, st, d, std = pair
+            y = ops.norm_apply(t1, st, True, EPS, act=ACT_RELU, out=t1)
+            x = ops.norm_apply(d, std, True, EPS, act=ACT_NONE, out=d)
+        elif pair is not None:
+            y, x = pair
+        else:
+            y = self._conv_norm(x, blk._p1, blk.norm1, ACT_RELU, take_res=fuse)
+            if blk.downsample is not None:
+                x = self._conv_norm(x, blk._pd, blk.norm3, ACT_NONE)
         return self._conv_norm(y, blk._p2, blk.norm2, ACT_RELU, res=x, lazy=lazy_out and self.norm_fn == "instance" and not torch.is_grad_enabled(),
                                defer_res=fuse)
 

@@ -1520,6 +1520,70 @@ def encoder_tail(x, m, w_frag: Tensor, bias: Tensor, w_fmt: int) -> Tensor:
     return y
 
 
+def conv_s2_pair_stats_parts(h: int, w: int) -> int:
+    """Statistics entries per (image, channel) of ff_conv_s2_pair_fwd over an h x w input: one per 4 x 16 output tile."""
+    return _hip.load().ff_conv_s2_pair_stats_parts(h, w)
+
+
+def conv_s2_pair_inputs_ok(x, cout: int) -> bool:
+    """ff_conv_s2_pair_fwd reads one fp32 NHWC tensor (a channel slice too) of a multiple of 32 channels, 16-byte aligned,
+    below 2 GiB, and writes 96 or 128 channels."""
+    if not isinstance(x, Tensor) or x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    b, h, w, c = x.shape
+    if c % 32 or cout not in (96, 128) or x.stride(3) != 1 or x.data_ptr() % 16 or b >= 65536:
+        return False
+    ld = x.stride(2) if w > 1 else (x.stride(1) if h > 1 else max(x.stride(0), c))
+    if ld % 4 or ld < c or (w > 1 and h > 1 and x.stride(1) != w * ld) or (b > 1 and x.stride(0) != h * w * ld):
+        return False
+    return b * h * w * ld * 4 < (1 << 31)
+
+
+def conv_s2_pair(x: Tensor, w3_frag: Tensor, w1_frag: Tensor, bias3: Optional[Tensor], bias1: Optional[Tensor], cout: int, w_fmt: int,
+                 scale=(None, None), shift=(None, None), act=(ACT_NONE, ACT_NONE), want_stats: bool = False, out=(None, None),
+                 kernels=((3, 2, 1), (1, 2, 0))):
+    """The entry of a stride-2 residual block as ONE launch (ff_conv_s2_pair_fwd): a = conv3x3(x), stride 2, pad 1 and
+    d = conv1x1(x), stride 2, pad 0 from one pass over x; w3_frag / w1_frag the two weights in fragment order (PackedConv.frag),
+    scale / shift / act per output (a folded eval BatchNorm) -> (a, d), or - want_stats - (a, stats_a, d, stats_d) with the
+    per-sample {sum, sum of squares} tables of norm_stats, from the launch's own epilogue.  `kernels`: (size, stride, pad) of the
+    two convolutions; what the kernel cannot read is refused by the library."""
+    _require_gpu(x)
+    b, h, w, cin = x.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    p = _hip.FFConvS2Pair()
+    p.x, p.x_ld = x.data_ptr(), _ld(x)
+    p.B, p.H, p.W, p.Cin, p.Cout = b, h, w, cin, cout
+    for i, (k, s, pd) in enumerate(kernels):
+        p.k[i], p.stride[i], p.pad[i] = k, s, pd
+    p.w3_frag, p.w1_frag, p.w_format = w3_frag.data_ptr(), w1_frag.data_ptr(), w_fmt
+    outs, parts = [], []
+    nparts = conv_s2_pair_stats_parts(h, w) if want_stats else 0
+    for i, bias in enumerate((bias3, bias1)):
+        y = out[i] if out[i] is not None else empty_nhwc(b, ho, wo, cout, x)
+        assert tuple(y.shape) == (b, ho, wo, cout)
+        outs.append(y)
+        p.y[i], p.y_ld[i] = y.data_ptr(), _ld(y)
+        p.bias[i] = bias.data_ptr() if bias is not None else None
+        if scale[i] is not None:
+            p.scale[i], p.shift[i] = scale[i].data_ptr(), shift[i].data_ptr()
+        p.act[i] = act[i]
+        if nparts:
+            parts.append(torch.empty(b * nparts * cout * 4, dtype=torch.float32, device=x.device))
+            p.stats_part[i] = parts[i].data_ptr()
+    if _range_word is not None:      # CHECK_RANGE: x goes through the split format like any convolution input
+        _range_probe(x)
+    # (timed with the convolutions in bench.py's roofline_conv: the useful FLOP of both convolutions)
+    _timed_call("conv", "ff_conv_s2_pair_fwd", C.byref(p), _stream(), note=(2.0 * b * ho * wo * cout * cin * 10, w_fmt))
+    if not want_stats:
+        return outs[0], outs[1]
+    stats = []
+    for i in range(2):
+        st = _zero_stats(b, cout, x.device)
+        _hip.call("ff_norm_stats_finish", _p(parts[i]), b, nparts, cout, _p(st), _stream())
+        stats.append(st)
+    return outs[0], stats[0], outs[1], stats[1]
+
+
 def mask_upsample_pack(w_split: Tensor) -> Tensor:
     """Split rows of the mask head's second convolution (576 x 256) -> ff_mask_upsample_fwd's stage-major weight image."""
     assert w_split.dtype == torch.uint8 and w_split.numel() == 576 * 1024 and w_split.is_contiguous()

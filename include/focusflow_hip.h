@@ -70,7 +70,9 @@ const char* ff_last_error(void);
  *   7 (unchanged): entry points only: ff_fb_dense, ff_fb_matches (forward-backward consistency of a video session: the
  *                occlusion map, and tracks culled by their round-trip error)
  *   7 (unchanged): entry points only: ff_epipolar_ws, ff_epipolar_ransac (epipolar check of a video session: a RANSAC
- *                fundamental matrix per pair, and tracks culled as its outliers) */
+ *                fundamental matrix per pair, and tracks culled as its outliers)
+ *   7 (unchanged): entry points only: ff_conv_s2_pair_fwd / ff_conv_s2_pair_stats_parts (FFConvS2Pair: the 3x3 and the 1x1
+ *                shortcut of a stride-2 residual block entry as one launch) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -623,6 +625,31 @@ typedef struct FFEncoderTail {
     int B, HW, C, Cout;
 } FFEncoderTail;
 int ff_encoder_tail_fwd(const FFEncoderTail* p, void* stream);
+/* ------------------------------------------------------------------------
+ * The entry of a stride-2 residual block (extractor.py:26-46) as one launch (csrc/conv_s2_pair.hip): from one input x
+ *     y[0] = act[0]((conv3x3(x; w3_frag), stride 2, pad 1) + bias[0]) * scale[0] + shift[0])      (conv1)
+ *     y[1] = act[1]((conv1x1(x; w1_frag), stride 2, pad 0) + bias[1]) * scale[1] + shift[1])      (downsample[0])
+ * x: fp32 NHWC, Cin a multiple of 32, x_ld >= Cin; Cout = 96 or 128 for both; w3_frag / w1_frag: the split rows
+ * [Cout][3][3][Cin] / [Cout][Cin] (ff_pack_conv_weight + ff_pack_split_f16) re-ordered by ff_pack_frag16; bias[i], scale[i],
+ * shift[i]: [Cout] or NULL (scale and shift together: a folded eval BatchNorm); k / stride / pad describe the two
+ * convolutions and must be (3, 2, 1) and (1, 2, 0); w_format FF_W_F16X3 / FF_W_F16.  stats_part[i] (or NULL): partial
+ * InstanceNorm statistics of y[i] in FFConvParams.stats_part's entry format, [B][ff_conv_s2_pair_stats_parts(H, W)][Cout][4],
+ * for ff_norm_stats_finish.  All tensors 16-byte aligned, leading dimensions multiples of 4, below 2 GiB, outputs aliasing
+ * neither x nor each other.  Anything else is refused.
+ * ---------------------------------------------------------------------- */
+typedef struct FFConvS2Pair {
+    const float* x;        int x_ld;
+    int B, H, W, Cin, Cout;
+    int k[2], stride[2], pad[2];     /* [0] the 3x3 convolution, [1] the 1x1 shortcut */
+    const void* w3_frag;   const void* w1_frag;
+    int w_format;
+    const float* bias[2];  const float* scale[2]; const float* shift[2];
+    int act[2];                      /* FF_ACT_* */
+    float* y[2];           int y_ld[2];
+    float* stats_part[2];
+} FFConvS2Pair;
+int ff_conv_s2_pair_stats_parts(int H, int W);
+int ff_conv_s2_pair_fwd(const FFConvS2Pair* p, void* stream);
 /* GRU gates (update.py:47-49): rh = r*h ; h' = (1-z)*h + z*q */
 int ff_gru_rh(const float* r, int r_ld, const float* h, int h_ld, float* rh, int rh_ld,
               long long npix, int C, void* stream);
