@@ -140,6 +140,11 @@ _SIGS = {
                       _fp, _fp, _fp, _fp, _fp, _fp],
     "ff_epipolar_ransac": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint, _fp, C.c_int, _fp, _fp, _fp, _fp,
                            _fp, _fp, _fp, _fp, _fp, _fp, _ll, _fp],
+    "ff_epipolar_ransac_hold": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint, _fp, C.c_int, _fp, _fp, _fp,
+                                _fp, _fp, _fp, _fp, _fp, _fp, _fp, _ll, _fp, _fp],
+    "ff_homography_ransac": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, _fp, C.c_int, _fp, _fp,
+                             _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _ll, _fp],
+    "ff_homography_residual": [_fp, _ll, _ll, _ll, _ll, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],
@@ -205,7 +210,7 @@ _SIGS = {
                          C.c_int, _fp],
 }
 EXPORTS = sorted(list(_SIGS) + ["ff_last_error", "ff_abi_version", "ff_corr_plane_elems", "ff_conv2d_splitk_hint", "ff_conv2d_stats_parts", "ff_fusion_pair_tile",
-                                 "ff_forward_interpolate_ws", "ff_good_features_ws", "ff_epipolar_ws", "ff_conv_s2_pair_stats_parts"])
+                                 "ff_forward_interpolate_ws", "ff_good_features_ws", "ff_epipolar_ws", "ff_homography_ws", "ff_conv_s2_pair_stats_parts"])
 
 ABI_VERSION = 7      # include/focusflow_hip.h: FF_ABI_VERSION
 _lib = None
@@ -265,6 +270,8 @@ def load():
     lib.ff_good_features_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_epipolar_ws.restype = C.c_int
     lib.ff_epipolar_ws.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.ff_homography_ws.restype = C.c_int
+    lib.ff_homography_ws.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ff_conv2d_stats_parts.restype = C.c_int
     lib.ff_conv2d_stats_parts.argtypes = [C.POINTER(FFConvParams)]
     lib.ff_conv_s2_pair_stats_parts.restype = C.c_int

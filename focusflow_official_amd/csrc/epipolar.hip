@@ -2,9 +2,10 @@
 // fundamental matrices (Fischler & Bolles 1981; normalised coordinates after Hartley 1997) on the rows of a matches / valid
 // pair, scored by the Sampson distance.  Definitions: include/focusflow_hip.h; restated in numpy by tests/epipolar_ref.py.
 // Every step is exact (fp32, every operation rounded separately: no FMA; the draws are a 32-bit integer hash), so the tests ask
-// for equality.
+// for equality.  What the homography check (homography.hip) shares with it - candidates, normalisation, hash, workspace, the
+// compaction launch, the elimination, the argmax - lives in ransac_common.h.
 //
-//   epi_compact_kernel      one block per sample: the candidate rows in row order (a prefix sum over N <= 4096), their
+//   epi_compact_kernel      (ransac_common.h) one block per sample: the candidate rows in row order (a prefix sum over N <= 4096), their
 //                           normalised coordinates as four planes, their number M
 //   epi_hypotheses_kernel   one thread per hypothesis: 8 distinct ranks (Floyd), the 8 x 9 system, elimination with full
 //                           pivoting, back-substitution.  The system lives in LDS as [element][thread]: a pivot's row and column are
@@ -18,36 +19,9 @@
 // element is written by exactly one thread: no atomics, no allocation, no synchronisation; every launch goes to the caller's
 // stream.
 #pragma clang fp contract(off)
-#include <climits>
-#include "ff_common.h"
+#include "ransac_common.h"
 
 namespace {
-
-constexpr int MAX_ROWS = 4096;      // N: the slots of a track table, the points of a detector
-constexpr int MAX_HYP = 4096;       // K
-constexpr int MAX_BATCH = 1024;    // B: a grid dimension, and the workspace stays below 2^31 bytes
-constexpr int BLOCK = 1024;         // compact and select: four rows per thread cover MAX_ROWS
-constexpr int WAVE = 64;
-constexpr int SCORE_WAVES = 4;      // hypotheses per block of the scoring kernel
-
-struct Frame {
-    float cx, cy, s;                // xn = (x - cx) s
-};
-
-__device__ __forceinline__ unsigned mix(unsigned x) {      // lowbias32
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ bool finite4(const float4 m) { return isfinite(m.x) && isfinite(m.y) && isfinite(m.z) && isfinite(m.w); }
-__device__ __forceinline__ bool candidate(const float4 m, unsigned char valid) { return valid && m.x >= 0.f && finite4(m); }
-__device__ __forceinline__ float4 normalise(const float4 m, const Frame fr) {
-    return make_float4((m.x - fr.cx) * fr.s, (m.y - fr.cy) * fr.s, (m.z - fr.cx) * fr.s, (m.w - fr.cy) * fr.s);
-}
 
 // The one expression of the scoring pass and of the final flags: x' F x squared, and the squared gradient norm.
 __device__ __forceinline__ void sampson(const float* f, const float4 p, float& num, float& den) {
@@ -60,76 +34,6 @@ __device__ __forceinline__ void sampson(const float* f, const float4 p, float& n
     num = e * e;
     den = ((fx0 * fx0 + fx1 * fx1) + ft0 * ft0) + ft1 * ft1;
 }
-
-// workspace of one call: M (B) int | planes (B,4,N) float | models (B,K,9) float | counts (B,K) int
-struct Workspace {
-    int* m;
-    float* planes;
-    float* models;
-    int* counts;
-};
-__host__ __device__ inline size_t ws_bytes(long long B, long long N, long long K) { return (size_t)(B * (1 + 4 * N + 9 * K + K)) * 4; }
-inline Workspace carve(void* ws, long long B, long long N, long long K) {
-    Workspace w;
-    w.m = static_cast<int*>(ws);
-    w.planes = reinterpret_cast<float*>(w.m + B);
-    w.models = w.planes + B * 4 * N;
-    w.counts = reinterpret_cast<int*>(w.models + B * K * 9);
-    return w;
-}
-
-// thread t takes rows 4 t .. 4 t + 3
-__global__ void __launch_bounds__(BLOCK) epi_compact_kernel(const float4* __restrict__ matches, const unsigned char* __restrict__ valid, int N, Frame fr,
-                                                            Workspace ws) {
-    __shared__ int wave_total[BLOCK / WAVE];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t % WAVE, wv = t / WAVE;
-    matches += (long long)b * N;
-    valid += (long long)b * N;
-    float4 m[4];
-    bool is[4];
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = 4 * t + j;
-        is[j] = false;
-        if (n < N) {
-            m[j] = matches[n];
-            is[j] = candidate(m[j], valid[n]);
-        }
-        mine += is[j];
-    }
-    int incl = mine;      // inclusive scan over the wave
-#pragma unroll
-    for (int d = 1; d < WAVE; d *= 2) {
-        const int up = __shfl_up(incl, d, WAVE);
-        if (lane >= d) incl += up;
-    }
-    if (lane == WAVE - 1) wave_total[wv] = incl;
-    __syncthreads();
-    int before = incl - mine, total = 0;
-#pragma unroll
-    for (int i = 0; i < BLOCK / WAVE; ++i) {
-        const int c = wave_total[i];
-        if (i < wv) before += c;
-        total += c;
-    }
-    float* planes = ws.planes + (long long)b * 4 * N;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (is[j]) {
-            const float4 p = normalise(m[j], fr);
-            planes[before] = p.x;
-            planes[N + before] = p.y;
-            planes[2 * N + before] = p.z;
-            planes[3 * N + before] = p.w;
-            ++before;
-        }
-    if (t == 0) ws.m[b] = total;
-}
-
-// A(r, c) of this thread's system, and the unknown a column stands for
-#define EPI_A(r, c) sys[((r) * 9 + (c)) * WAVE + lane]
-#define EPI_PERM(c) perm[(c) * WAVE + lane]
 
 __global__ void __launch_bounds__(WAVE) epi_hypotheses_kernel(int N, int K, unsigned seed, const int* __restrict__ epoch, Workspace ws) {
     __shared__ float sys[72 * WAVE];
@@ -170,50 +74,7 @@ __global__ void __launch_bounds__(WAVE) epi_hypotheses_kernel(int N, int K, unsi
         EPI_A(j, 7) = y;
         EPI_A(j, 8) = 1.f;
     }
-#pragma unroll
-    for (int c = 0; c < 9; ++c) EPI_PERM(c) = c;
-    bool good = true;
-#pragma unroll 1
-    for (int p = 0; p < 8; ++p) {
-        float big = 0.f;
-        int pr = p, pc = p;
-        for (int r = p; r < 8; ++r)
-            for (int c = p; c < 9; ++c) {
-                const float a = fabsf(EPI_A(r, c));
-                if (a > big) big = a, pr = r, pc = c;      // (strict: the first of equal entries in (row, column) order)
-            }
-        good = good && big > 0.f;
-        for (int c = 0; c < 9; ++c) {      // (pr == p or pc == p: a swap with itself)
-            const float u = EPI_A(p, c), v = EPI_A(pr, c);
-            EPI_A(p, c) = v;
-            EPI_A(pr, c) = u;
-        }
-        for (int r = 0; r < 8; ++r) {
-            const float u = EPI_A(r, p), v = EPI_A(r, pc);
-            EPI_A(r, p) = v;
-            EPI_A(r, pc) = u;
-        }
-        const int u = EPI_PERM(p), v = EPI_PERM(pc);
-        EPI_PERM(p) = v;
-        EPI_PERM(pc) = u;
-        const float pivot = EPI_A(p, p);
-        for (int r = p + 1; r < 8; ++r) {
-            const float factor = __fdiv_rn(EPI_A(r, p), pivot);
-            for (int c = p + 1; c < 9; ++c) EPI_A(r, c) = EPI_A(r, c) - factor * EPI_A(p, c);
-        }
-    }
-    // back-substitution, the free unknown 1; z(i) takes the place of A(i, 8)
-    float* model = ws.models + ((long long)b * K + k) * 9;
-    model[EPI_PERM(8)] = 1.f;
-#pragma unroll 1
-    for (int i = 7; i >= 0; --i) {
-        float acc = EPI_A(i, 8);
-        for (int c = i + 1; c < 8; ++c) acc = acc + EPI_A(i, c) * EPI_A(c, 8);
-        const float z = __fdiv_rn(-acc, EPI_A(i, i));
-        EPI_A(i, 8) = z;
-        good = good && isfinite(z);
-        model[EPI_PERM(i)] = z;
-    }
+    const bool good = solve_8x9(sys, perm, lane, ws.models + ((long long)b * K + k) * 9);
     *count = good ? 0 : -1;
 }
 
@@ -249,30 +110,13 @@ __global__ void __launch_bounds__(BLOCK) epi_select_kernel(const float4* __restr
                                                            long long* __restrict__ ids, int* __restrict__ age, float* __restrict__ F,
                                                            float* __restrict__ dist2, unsigned char* __restrict__ status,
                                                            int* __restrict__ inliers, int* __restrict__ candidates, unsigned char* __restrict__ ok_out,
-                                                           int* __restrict__ epoch, Workspace ws) {
-    __shared__ int best_count[BLOCK / WAVE], best_k[BLOCK / WAVE];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid % WAVE, wv = tid / WAVE;
-    const int* counts = ws.counts + (long long)b * K;
-    int bc = -1, bk = INT_MAX;      // the largest count, the lowest k among equal ones
-    for (int k = tid; k < K; k += BLOCK) {
-        const int c = counts[k];
-        if (c > bc) bc = c, bk = k;      // (k ascends within a thread)
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d >= 1; d /= 2) {
-        const int oc = __shfl_xor(bc, d, WAVE), okk = __shfl_xor(bk, d, WAVE);
-        if (oc > bc || (oc == bc && okk < bk)) bc = oc, bk = okk;
-    }
-    if (lane == 0) best_count[wv] = bc, best_k[wv] = bk;
-    __syncthreads();
-    bc = best_count[0], bk = best_k[0];
-#pragma unroll
-    for (int i = 1; i < BLOCK / WAVE; ++i) {
-        const int oc = best_count[i], okk = best_k[i];
-        if (oc > bc || (oc == bc && okk < bk)) bc = oc, bk = okk;
-    }
+                                                           int* __restrict__ epoch, const unsigned char* __restrict__ hold, Workspace ws) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int bc, bk;
+    best_hypothesis(ws.counts + (long long)b * K, K, bc, bk);
     const int M = ws.m[b];
-    const bool ok = M >= 8 && bc >= min_inliers && 1000ll * bc >= (long long)permille * M;
+    const bool held = hold && hold[b];      // (ff_epipolar_ransac_hold: this sample gets no verdict, whatever its hypotheses scored)
+    const bool ok = !held && M >= 8 && bc >= min_inliers && 1000ll * bc >= (long long)permille * M;
     float f[9];
     const float* model = ws.models + ((long long)b * K + bk) * 9;
 #pragma unroll
@@ -331,21 +175,16 @@ __global__ void __launch_bounds__(BLOCK) epi_select_kernel(const float4* __restr
 
 }  // namespace
 
-#define FF_REQUIRE_EPI_SHAPE(name)                                                                                       \
-    FF_REQUIRE(B > 0 && B <= MAX_BATCH, name ": B = %d (1 .. %d samples)", B, MAX_BATCH);                                   \
-    FF_REQUIRE(N >= 1 && N <= MAX_ROWS, name ": N = %d (1 .. %d rows)", N, MAX_ROWS);                                    \
-    FF_REQUIRE(K >= 1 && K <= MAX_HYP, name ": K = %d (1 .. %d hypotheses)", K, MAX_HYP)
-
 extern "C" int ff_epipolar_ws(int B, int N, int K) {
     if (B <= 0 || B > MAX_BATCH || N < 1 || N > MAX_ROWS || K < 1 || K > MAX_HYP) return 0;
     return (int)ws_bytes(B, N, K);
 }
 
-extern "C" int ff_epipolar_ransac(const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K, int min_inliers,
-                                  int permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids, int* age, float* F,
-                                  float* dist2, unsigned char* status, int* inliers, int* candidates, unsigned char* ok, void* ws,
-                                  long long ws_size, void* stream) {
-    FF_REQUIRE_EPI_SHAPE("ff_epipolar_ransac");
+extern "C" int ff_epipolar_ransac_hold(const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K,
+                                       int min_inliers, int permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids, int* age,
+                                       float* F, float* dist2, unsigned char* status, int* inliers, int* candidates, unsigned char* ok, void* ws,
+                                       long long ws_size, const unsigned char* hold, void* stream) {
+    FF_REQUIRE_RANSAC_SHAPE("ff_epipolar_ransac");
     FF_REQUIRE(H > 0 && W > 0 && H <= (1 << 24) && W <= (1 << 24), "ff_epipolar_ransac: H = %d, W = %d (1 .. 2^24: positions are fp32)", H, W);
     FF_REQUIRE(threshold >= 0.f && threshold < __builtin_inff(), "ff_epipolar_ransac: threshold = %g (>= 0 and finite, no NaN)", (double)threshold);
     FF_REQUIRE(min_inliers >= 1, "ff_epipolar_ransac: min_inliers = %d (at least 1: a degenerate hypothesis scores 0)", min_inliers);
@@ -355,8 +194,7 @@ extern "C" int ff_epipolar_ransac(const float* matches, unsigned char* valid, in
     FF_REQUIRE(((size_t)matches & 15) == 0 && ((size_t)pos & 7) == 0, "ff_epipolar_ransac: matches must be 16-byte aligned, pos 8-byte aligned");
     FF_REQUIRE(((size_t)ws & 15) == 0 && ws_size >= (long long)ws_bytes(B, N, K), "ff_epipolar_ransac: ws must be 16-byte aligned and hold %lld bytes, got %lld",
                (long long)ws_bytes(B, N, K), ws_size);
-    const double sd = 2.0 / ((double)H + (double)W);
-    const Frame fr = {(float)((W - 1) / 2.0), (float)((H - 1) / 2.0), (float)sd};
+    const Frame fr = frame_of(H, W);
     const float t = (float)((double)threshold * (double)threshold * (double)fr.s * (double)fr.s), s2 = (float)((double)fr.s * (double)fr.s);
     const Workspace w = carve(ws, B, N, K);
     const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -365,6 +203,14 @@ extern "C" int ff_epipolar_ransac(const float* matches, unsigned char* valid, in
     epi_hypotheses_kernel<<<dim3((K + WAVE - 1) / WAVE, B), WAVE, 0, s>>>(N, K, seed, epoch, w);
     epi_score_kernel<<<dim3((K + SCORE_WAVES - 1) / SCORE_WAVES, B), SCORE_WAVES * WAVE, 0, s>>>(N, K, t, w);
     epi_select_kernel<<<B, BLOCK, 0, s>>>(m4, valid, N, K, fr, t, s2, min_inliers, permille, cull, reinterpret_cast<float2*>(pos), ids, age, F, dist2,
-                                          status, inliers, candidates, ok, epoch, w);
+                                          status, inliers, candidates, ok, epoch, hold, w);
     return ff::check_launch("ff_epipolar_ransac");
+}
+
+extern "C" int ff_epipolar_ransac(const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K, int min_inliers,
+                                  int permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids, int* age, float* F,
+                                  float* dist2, unsigned char* status, int* inliers, int* candidates, unsigned char* ok, void* ws,
+                                  long long ws_size, void* stream) {
+    return ff_epipolar_ransac_hold(matches, valid, B, N, H, W, threshold, K, min_inliers, permille, seed, epoch, cull, pos, ids, age, F, dist2, status,
+                                   inliers, candidates, ok, ws, ws_size, nullptr, stream);
 }

@@ -44,13 +44,22 @@ round-trip-consistent ones.
                                              # outlier, 4 no verdict), (B,N) fp32 Sampson distance in px^2; where there is a
                                              # verdict res.valid is cleared for the outliers, and with tracks their slots have died
     res.epi.inliers, res.epi.candidates      # (B) int32
+
+With homography=True (or homography=geometry.Homography(...)) the step asks, behind fb= and before epipolar=, whether ONE
+homography explains the pair - a planar scene, a camera that only rotates - (csrc/homography.hip), holds the epipolar check back
+where it does (F is under-determined there), and with Homography.dense writes the residual of the flow against the map:
+
+    seq = FrameSequence(model, raft_iters=12, keypoints=GoodFeatures(), tracks=True, epipolar=True, homography=True)
+    res.hom.H, res.hom.ok, res.hom.planar    # (B,3,3) fp32 in pixel coordinates, (x', y', 1) ~ H (x, y, 1); (B) uint8; (B) uint8
+    res.hom.status, res.hom.dist2            # per row of res.matches, as res.epi's; the squared transfer error in px^2
+    res.hom.residual                         # dense=True: (B,H,W) fp32 px^2, -1 without a verdict; else None
 """
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import ops
-from .geometry import EpiResult, EpipolarCheck, as_epipolar
+from .geometry import EpiResult, EpipolarCheck, HomResult, HomographyCheck, as_epipolar, as_homography
 from .model import FF_RAFT_FUSION
 from .tracks import MAX_SLOTS, TrackResult, TrackTable
 
@@ -83,15 +92,17 @@ class FrameResult(tuple):
     behind those: a CheckedFrameResult (six items) or a TrackedCheckedFrameResult (seven).  Without either the tuple has the five
     items it always had, so a caller that unpacks or walks them goes on working, and `.tracks` and `.fb` are None.  A session with
     epipolar= gets the shape it would have without, plus a last item `epi` (a geometry.EpiResult): Epi-, TrackedEpi-, CheckedEpi-
-    and TrackedCheckedEpiFrameResult; `.epi` is None in the four shapes without.  All eight behave as typing.NamedTuple classes do:
-    `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
+    and TrackedCheckedEpiFrameResult; `.epi` is None in the four shapes without.  A session with homography= likewise gets the
+    shape it would have without, plus a last item `hom` (a geometry.HomResult): each of the eight has a generated subclass whose
+    name puts Hom before FrameResult (HomFrameResult .. TrackedCheckedEpiHomFrameResult); `.hom` is None in the eight without.  All
+    sixteen behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
     __slots__ = ()
     _fields = ("flow_low", "flow_up", "matches", "valid", "count")
 
     def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None, fb: Optional[FBResult] = None,
-                epi: Optional[EpiResult] = None):
-        extras = tuple(x for x in (tracks, fb, epi) if x is not None)
-        shape = _SHAPES[(tracks is not None, fb is not None, epi is not None)]
+                epi: Optional[EpiResult] = None, hom: Optional[HomResult] = None):
+        extras = tuple(x for x in (tracks, fb, epi, hom) if x is not None)
+        shape = _SHAPES[(tracks is not None, fb is not None, epi is not None, hom is not None)]
         return tuple.__new__(shape, (flow_low, flow_up, matches, valid, count) + extras)
 
     flow_low = property(lambda self: self[0])
@@ -102,20 +113,21 @@ class FrameResult(tuple):
     tracks = property(lambda self: None)
     fb = property(lambda self: None)
     epi = property(lambda self: None)
+    hom = property(lambda self: None)
 
     def __getnewargs__(self):      # (copy, deepcopy and pickle rebuild through __new__, item by item)
-        return tuple(self[:5]) + (self.tracks, self.fb, self.epi)
+        return tuple(self[:5]) + (self.tracks, self.fb, self.epi, self.hom)
 
     @classmethod
     def _make(cls, iterable):
-        """From the items of any of the eight shapes; an item behind the fifth is `fb` if it is an FBResult, `epi` if it is an
-        EpiResult, else `tracks`."""
+        """From the items of any of the sixteen shapes; an item behind the fifth is `fb` if it is an FBResult, `epi` if it is an
+        EpiResult, `hom` if it is a HomResult, else `tracks`."""
         items = tuple(iterable)
-        if len(items) <= 5 or len(items) > 8:
+        if len(items) <= 5 or len(items) > 9:
             return FrameResult(*items)      # (too few or too many: the TypeError of __new__)
         extras = {}
         for x in items[5:]:
-            name = "fb" if isinstance(x, FBResult) else "epi" if isinstance(x, EpiResult) else "tracks"
+            name = "fb" if isinstance(x, FBResult) else "epi" if isinstance(x, EpiResult) else "hom" if isinstance(x, HomResult) else "tracks"
             if name in extras:
                 raise TypeError(f"FrameResult._make: two items for `{name}`")
             extras[name] = x
@@ -125,7 +137,7 @@ class FrameResult(tuple):
         return dict(zip(self._fields, self))
 
     def _replace(self, **kwargs):
-        unknown = set(kwargs) - set(TrackedCheckedEpiFrameResult._fields)
+        unknown = set(kwargs) - set(FrameResult._fields + ("tracks", "fb", "epi", "hom"))
         if unknown:
             raise ValueError(f"Got unexpected field names: {sorted(unknown)!r}")
         return FrameResult(**{**self._asdict(), **kwargs})
@@ -188,10 +200,23 @@ class TrackedCheckedEpiFrameResult(FrameResult):
     epi = property(lambda self: self[7])
 
 
-# (tracks, fb, epi) present -> the shape
-_SHAPES = {(False, False, False): FrameResult, (True, False, False): TrackedFrameResult, (False, True, False): CheckedFrameResult,
-           (True, True, False): TrackedCheckedFrameResult, (False, False, True): EpiFrameResult, (True, False, True): TrackedEpiFrameResult,
-           (False, True, True): CheckedEpiFrameResult, (True, True, True): TrackedCheckedEpiFrameResult}
+def _with_hom(base):
+    """The shape of `base` plus a last item `hom`: a subclass of it, so `tracks`, `fb` and `epi` stay where they are."""
+    name = base.__name__.replace("FrameResult", "HomFrameResult")
+    return type(name, (base,), {"__slots__": (), "__module__": __name__, "__qualname__": name, "_fields": base._fields + ("hom",),
+                                "hom": property(lambda self: self[-1]),
+                                "__doc__": f"A {base.__name__} of a session with homography=: {len(base._fields) + 1} items, the last one `hom`.  "
+                                           "Made by FrameResult(..., hom=...)."})
+
+
+# (tracks, fb, epi, hom) present -> the shape; the eight with hom are generated (pickle finds them in this module by name)
+_SHAPES = {(False, False, False, False): FrameResult, (True, False, False, False): TrackedFrameResult, (False, True, False, False): CheckedFrameResult,
+           (True, True, False, False): TrackedCheckedFrameResult, (False, False, True, False): EpiFrameResult,
+           (True, False, True, False): TrackedEpiFrameResult, (False, True, True, False): CheckedEpiFrameResult,
+           (True, True, True, False): TrackedCheckedEpiFrameResult}
+for _key, _base in list(_SHAPES.items()):
+    _SHAPES[_key[:3] + (True,)] = globals()[_base.__name__.replace("FrameResult", "HomFrameResult")] = _with_hom(_base)
+del _key, _base
 
 
 class FrameSequence:
@@ -244,12 +269,22 @@ class FrameSequence:
     other buffers.  The result then carries `epi` (a geometry.EpiResult) as its last item.  F is neither forced to rank 2 nor
     refitted: see geometry.
 
+    homography=True or homography=geometry.Homography(...) (needs keypoints=): behind the forward-backward check and BEFORE the
+    epipolar one the step runs ops.homography_ransac on the pair's matches / valid: does one homography - a planar scene, a camera
+    that only rotates - explain the pair?  Homography.cull is False by default: the check then judges a copy of `valid` and touches
+    neither `valid` nor the table, so the epipolar check behind it sees the same candidates (the outliers of a homography are
+    the points off the plane, and HomResult.status names them); with cull it clears `valid` and kills the slots of its outliers
+    as the epipolar check does.  With epipolar= and Homography.hold_epipolar a pair whose `planar` is set gets no epipolar verdict (its F would be
+    arbitrary), by ops.epipolar_ransac(hold=hom.planar) inside the same graph.  With Homography.dense, ops.homography_residual
+    writes what is left of the cropped flow_up once H's motion is removed.  The check has an epoch word of its own, kept as the
+    epipolar one is.  The result then carries `hom` (a geometry.HomResult) as its last item.
+
     The tensors of a result are the session's static buffers: valid until the next push.  A frame in pinned host memory is
     read by an asynchronous copy: leave it alone until work enqueued after the push has finished (the event a consumer
     waits for anyway before it reads the matches)."""
 
     def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel",
-                 tracks=None, fb=None, epipolar=None):
+                 tracks=None, fb=None, epipolar=None, homography=None):
         if not isinstance(model, FF_RAFT_FUSION):
             raise ValueError(f"model: FrameSequence drives FF_RAFT_FUSION, whose forward takes flow_init; {type(model).__name__} "
                              "(FF_PWCNET has no flow_init) runs pair by pair through graph.GraphedForward")
@@ -278,6 +313,9 @@ class FrameSequence:
         self.epipolar = as_epipolar(epipolar)      # the geometry.Epipolar of the session; None: no epipolar check
         if self.epipolar is not None and keypoints is None:
             raise ValueError("epipolar: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
+        self.homography = as_homography(homography)      # the geometry.Homography of the session; None: no homography check
+        if self.homography is not None and keypoints is None:
+            raise ValueError("homography: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
         self._reads_mask = getattr(model, "mask_modal", None) is not None
         self._require_eval()
         self._key = None
@@ -293,6 +331,7 @@ class FrameSequence:
         self._table = None
         self._fb_mask = self._fb_mask_det = self._fb_init = self._guard_words_bw = None
         self._epi = None      # the geometry.EpipolarCheck: workspace, outputs, the epoch word
+        self._hom = self._hom_valid = None      # the geometry.HomographyCheck: the same, and the dense residual; the copy of `valid` it judges without cull
         self._frames = 0      # frames of the running sequence that have been ingested
 
     @property
@@ -396,6 +435,11 @@ class FrameSequence:
         if self.epipolar is not None:
             self._epi = EpipolarCheck(self.epipolar)
             self._epi.prepare(b, self._slots or self.keypoints.max_corners, device)      # (now, not inside a capture)
+        if self.homography is not None:
+            self._hom = HomographyCheck(self.homography)
+            self._hom.prepare(b, self._slots or self.keypoints.max_corners, device, h, w)
+            if not self.homography.cull:
+                self._hom_valid = torch.zeros((b, self._slots or self.keypoints.max_corners), dtype=torch.uint8, device=device)
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -432,10 +476,17 @@ class FrameSequence:
         elif det is not None:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
         fb = self._check(flow_low, flow_up, matches, valid) if self.fb is not None else None
-        epi = None
+        table = None if tb is None else (tb.pos, tb.ids, tb.age)
+        flow_up = flow_up[:, :, top:top + h, left:left + w]
+        epi = hom = None
+        if self._hom is not None:      # behind fb, before epipolar: both see the same candidates unless Homography.cull
+            # (without cull the check judges a copy of `valid`: off-plane rows stay candidates of the epipolar check and of the consumer)
+            judged = valid if self.homography.cull else self._hom_valid.copy_(valid)
+            hom = self._hom(matches, judged, h, w, table=table, flow=flow_up if self.homography.dense else None)
         if self._epi is not None:      # last: its candidates are the rows that are still valid
-            epi = self._epi(matches, valid, h, w, table=None if tb is None else (tb.pos, tb.ids, tb.age))
-        return FrameResult(flow_low, flow_up[:, :, top:top + h, left:left + w], matches, valid, count, tracks, fb, epi)
+            hold = hom.planar if hom is not None and self.homography.hold_epipolar else None
+            epi = self._epi(matches, valid, h, w, table=table, hold=hold)
+        return FrameResult(flow_low, flow_up, matches, valid, count, tracks, fb, epi, hom)
 
     def _check(self, flow_low, flow_up, matches, valid):
         """The forward-backward part of a step, behind the advance / the matches: the backward pair's mask, the backward flow's
@@ -481,8 +532,9 @@ class FrameSequence:
         """graph.GraphedForward's capture around `_step`: warm-up steps on a side stream (they pack weights, set kernel
         attributes, decide the routes and warm the allocator), what they changed put back, then the capture with static
         guard words."""
-        epoch = self._epi.epoch if self._epi is not None else None      # (the warm-up steps would spend epochs: graph and eager draw alike)
-        keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init, epoch) if t is not None]
+        # (the warm-up steps would spend epochs: graph and eager draw alike)
+        epochs = [c.epoch for c in (self._epi, self._hom) if c is not None]
+        keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init, *epochs) if t is not None]
         table = self._table.state() if self._table is not None else None      # (the warm-up steps would move tracks and spend ids)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())

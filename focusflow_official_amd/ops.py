@@ -1282,20 +1282,8 @@ def epipolar_ws(b: int, n: int, hypotheses: int) -> int:
     return _hip.load().ff_epipolar_ws(int(b), int(n), int(hypotheses))
 
 
-def epipolar_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: float, hypotheses: int, min_inliers: int, permille: int, seed: int,
-                    epoch: Tensor, table=None, cull: bool = True, out=None, ws: Optional[Tensor] = None):
-    """The epipolar check of the rows of a matches / valid pair (csrc/epipolar.hip; the definition is in include/focusflow_hip.h):
-    a RANSAC over `hypotheses` 8-point fundamental matrices in coordinates normalised by the h x w frame, scored by the Sampson
-    distance against `threshold` px.  matches (B,N,4) fp32 [x, y, x', y'] and valid (B,N) uint8 as keypoint_matches,
-    tracks_advance or fb_matches left them; the candidates are the rows with valid = 1.  There is a verdict where at least 8
-    candidates exist and the best model has at least min_inliers inliers and permille / 1000 of the candidates; then `valid` is
-    cleared in place where a candidate is an outlier, and with cull and a table (pos, ids, age) whose slots are the rows those
-    slots die.  epoch: one int32 on the device, read by the draws and incremented by the call.  -> (F (B,3,3) fp32 in pixel
-    coordinates, x'^t F x = 0, zeros without a verdict; inliers (B) int32; candidates (B) int32; ok (B) uint8; status (B,N) uint8:
-    0 no row, 1 inlier, 2 not a candidate, 3 outlier, 4 candidate but no verdict; dist2 (B,N) fp32 px^2: -1 no row, +inf without a
-    verdict); out: that tuple to write into (default: new tensors).  ws: a uint8 device tensor of epipolar_ws(B, N, hypotheses)
-    bytes to work in (default: a new one per call).  Exact.  Enqueues only, so it can be captured."""
-    name = "epipolar_ransac"
+def _ransac_args(name: str, matches: Tensor, valid: Tensor, epoch: Tensor, table):
+    """What epipolar_ransac and homography_ransac ask of their common arguments.  -> (B, N, device, pos, ids, age)"""
     _require_device(matches, name, "matches", (torch.float32,))
     _require_device(valid, name, "valid", (torch.uint8,))
     if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
@@ -1314,20 +1302,105 @@ def epipolar_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: f
         pos, ids, age = table
         if _track_table(name, pos, ids, age) != (b, n) or pos.device != dev:
             raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {dev}, got pos {tuple(pos.shape)} on {pos.device}")
+    return b, n, dev, pos, ids, age
+
+
+def _ransac_ws(name: str, ws: Optional[Tensor], nbytes: int, dev) -> Tensor:
+    if ws is None:
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # (an unsupported shape is refused by the call itself, with its reason)
+    _require_device(ws, name, "ws", (torch.uint8,))
+    if ws.numel() < nbytes or not ws.is_contiguous() or ws.device != dev:
+        raise _hip.FocusFlowHipError(f"{name}: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, got {ws.numel()} on {ws.device}")
+    return ws
+
+
+def epipolar_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: float, hypotheses: int, min_inliers: int, permille: int, seed: int,
+                    epoch: Tensor, table=None, cull: bool = True, out=None, ws: Optional[Tensor] = None, hold: Optional[Tensor] = None):
+    """The epipolar check of the rows of a matches / valid pair (csrc/epipolar.hip; the definition is in include/focusflow_hip.h):
+    a RANSAC over `hypotheses` 8-point fundamental matrices in coordinates normalised by the h x w frame, scored by the Sampson
+    distance against `threshold` px.  matches (B,N,4) fp32 [x, y, x', y'] and valid (B,N) uint8 as keypoint_matches,
+    tracks_advance or fb_matches left them; the candidates are the rows with valid = 1.  There is a verdict where at least 8
+    candidates exist and the best model has at least min_inliers inliers and permille / 1000 of the candidates; then `valid` is
+    cleared in place where a candidate is an outlier, and with cull and a table (pos, ids, age) whose slots are the rows those
+    slots die.  epoch: one int32 on the device, read by the draws and incremented by the call.  -> (F (B,3,3) fp32 in pixel
+    coordinates, x'^t F x = 0, zeros without a verdict; inliers (B) int32; candidates (B) int32; ok (B) uint8; status (B,N) uint8:
+    0 no row, 1 inlier, 2 not a candidate, 3 outlier, 4 candidate but no verdict; dist2 (B,N) fp32 px^2: -1 no row, +inf without a
+    verdict); out: that tuple to write into (default: new tensors).  ws: a uint8 device tensor of epipolar_ws(B, N, hypotheses)
+    bytes to work in (default: a new one per call).  hold: None, or (B) uint8 on the device (ff_epipolar_ransac_hold): a sample
+    whose byte is not 0 gets no verdict - ok 0, F zero, valid and the table left alone -, as homography_ransac's `planar` asks
+    where F is under-determined.  Exact.  Enqueues only, so it can be captured."""
+    name = "epipolar_ransac"
+    b, n, dev, pos, ids, age = _ransac_args(name, matches, valid, epoch, table)
     F, inliers, candidates, ok, status, dist2 = _track_outs(name, out, (("F", (b, 3, 3), torch.float32), ("inliers", (b,), torch.int32),
                                                                         ("candidates", (b,), torch.int32), ("ok", (b,), torch.uint8),
                                                                         ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
-    nbytes = epipolar_ws(b, n, hypotheses)
-    if ws is None:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # (an unsupported shape is refused by the call itself, with its reason)
+    ws = _ransac_ws(name, ws, epipolar_ws(b, n, hypotheses), dev)
+    args = (_p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), int(permille), int(seed) & 0xffffffff,
+            _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(F), _p(dist2), _p(status), _p(inliers), _p(candidates), _p(ok), _p(ws), ws.numel())
+    if hold is None:
+        _hip.call("ff_epipolar_ransac", *args, _stream())
     else:
-        _require_device(ws, name, "ws", (torch.uint8,))
-        if ws.numel() < nbytes or not ws.is_contiguous() or ws.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, got {ws.numel()} on {ws.device}")
-    _hip.call("ff_epipolar_ransac", _p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), int(permille),
-              int(seed) & 0xffffffff, _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(F), _p(dist2), _p(status), _p(inliers), _p(candidates),
-              _p(ok), _p(ws), ws.numel(), _stream())
+        _require_device(hold, name, "hold", (torch.uint8,))
+        if tuple(hold.shape) != (b,) or not hold.is_contiguous() or hold.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: hold must be contiguous {(b,)} on {dev}, got {tuple(hold.shape)} on {hold.device}")
+        _hip.call("ff_epipolar_ransac_hold", *args, _p(hold), _stream())
     return F, inliers, candidates, ok, status, dist2
+
+
+def homography_ws(b: int, n: int, hypotheses: int) -> int:
+    """Bytes of workspace ff_homography_ransac needs for (B, N, K); 0: the shape is not supported."""
+    return _hip.load().ff_homography_ws(int(b), int(n), int(hypotheses))
+
+
+def homography_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: float, hypotheses: int, min_inliers: int, permille: int,
+                      planar_permille: int, seed: int, epoch: Tensor, table=None, cull: bool = False, out=None, ws: Optional[Tensor] = None):
+    """The homography check of the rows of a matches / valid pair (csrc/homography.hip; the definition is in
+    include/focusflow_hip.h): a RANSAC over `hypotheses` 4-point homographies (DLT) in coordinates normalised by the h x w frame,
+    scored by the transfer error in the second image against `threshold` px.  Arguments as epipolar_ransac.  There is a verdict
+    where at least 4 candidates exist and the best model has at least min_inliers inliers and permille / 1000 of the candidates;
+    the pair is `planar` (one plane, or a camera that only rotates) where it also has planar_permille / 1000 of them.  With a
+    verdict `valid` is cleared in place where a candidate is an outlier, and with cull and a table those slots die.
+    -> (H (B,3,3) fp32 in pixel coordinates, (x', y', 1) ~ H (x, y, 1), zeros without a verdict; inliers (B) int32; candidates (B)
+    int32; ok (B) uint8; planar (B) uint8; status (B,N) uint8 as epipolar_ransac; dist2 (B,N) fp32 px^2: -1 no row, +inf without a
+    verdict and where the map sends the point behind the plane at infinity); out: that tuple to write into.  ws: a uint8 device
+    tensor of homography_ws(B, N, hypotheses) bytes.  Exact.  Enqueues only, so it can be captured."""
+    name = "homography_ransac"
+    b, n, dev, pos, ids, age = _ransac_args(name, matches, valid, epoch, table)
+    if matches.data_ptr() % 16:
+        raise _hip.FocusFlowHipError(f"{name}: matches must be 16-byte aligned (a view that starts inside a row is not)")
+    H, inliers, candidates, ok, planar, status, dist2 = _track_outs(
+        name, out, (("H", (b, 3, 3), torch.float32), ("inliers", (b,), torch.int32), ("candidates", (b,), torch.int32), ("ok", (b,), torch.uint8),
+                    ("planar", (b,), torch.uint8), ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
+    ws = _ransac_ws(name, ws, homography_ws(b, n, hypotheses), dev)
+    _hip.call("ff_homography_ransac", _p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), int(permille),
+              int(planar_permille), int(seed) & 0xffffffff, _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(H), _p(dist2), _p(status),
+              _p(inliers), _p(candidates), _p(ok), _p(planar), _p(ws), ws.numel(), _stream())
+    return H, inliers, candidates, ok, planar, status, dist2
+
+
+def homography_residual(flow: Tensor, H: Tensor, ok: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The dense residual of a flow field against the homographies of homography_ransac (csrc/homography.hip; the definition is
+    in include/focusflow_hip.h).  flow (B,2,h,w) fp32 with ANY strides - the unpadded crop of a padded flow is passed as the view
+    it is -, H (B,3,3) fp32 in pixel coordinates of that frame, ok (B) uint8.  -> (B,h,w) fp32: |(x + u, y + v) - pi(H (x, y, 1))|^2
+    in px^2, +inf where the map's w <= 0, -1 over a sample with ok = 0; out: a contiguous tensor to write into.  One launch, one
+    pass.  Exact.  Enqueues only, so it can be captured."""
+    name = "homography_residual"
+    _require_device(flow, name, "flow", (torch.float32,))
+    if flow.dim() != 4 or flow.shape[1] != 2 or flow.numel() == 0:
+        raise _hip.FocusFlowHipError(f"{name}: flow must be (B,2,h,w), got {tuple(flow.shape)}")
+    b, _, h, w = flow.shape
+    dev = flow.device
+    _require_device(H, name, "H", (torch.float32,))
+    _require_device(ok, name, "ok", (torch.uint8,))
+    if tuple(H.shape) != (b, 3, 3) or not H.is_contiguous() or H.device != dev:
+        raise _hip.FocusFlowHipError(f"{name}: H must be contiguous {(b, 3, 3)} on {dev}, got {tuple(H.shape)} on {H.device}")
+    if tuple(ok.shape) != (b,) or not ok.is_contiguous() or ok.device != dev:
+        raise _hip.FocusFlowHipError(f"{name}: ok must be contiguous {(b,)} on {dev}, got {tuple(ok.shape)} on {ok.device}")
+    if any(s < 0 for s in flow.stride()):
+        raise _hip.FocusFlowHipError(f"{name}: flow has a negative stride: {flow.stride()}")
+    out = _padded_out(name, out, (b, h, w), dev)
+    _hip.call("ff_homography_residual", _p(flow), flow.stride(0), flow.stride(1), flow.stride(2), flow.stride(3), _p(H), _p(ok), b, h, w, _p(out), _stream())
+    return out
 
 
 _minus_one = {}      # device -> the one-element tensor -1.0 that negate() scales by

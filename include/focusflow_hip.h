@@ -72,7 +72,10 @@ const char* ff_last_error(void);
  *   7 (unchanged): entry points only: ff_epipolar_ws, ff_epipolar_ransac (epipolar check of a video session: a RANSAC
  *                fundamental matrix per pair, and tracks culled as its outliers)
  *   7 (unchanged): entry points only: ff_conv_s2_pair_fwd / ff_conv_s2_pair_stats_parts (FFConvS2Pair: the 3x3 and the 1x1
- *                shortcut of a stride-2 residual block entry as one launch) */
+ *                shortcut of a stride-2 residual block entry as one launch)
+ *   7 (unchanged): entry points only: ff_homography_ws, ff_homography_ransac, ff_homography_residual, ff_epipolar_ransac_hold
+ *                (homography check of a video session: a RANSAC homography per pair, a planar / pure-rotation verdict that can
+ *                hold the epipolar check back, and the dense residual of the flow against the map) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -550,6 +553,56 @@ int ff_epipolar_ransac(const float* matches, unsigned char* valid, int B, int N,
                        int permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids, int* age, float* F,
                        float* dist2, unsigned char* status, int* inliers, int* candidates, unsigned char* ok, void* ws,
                        long long ws_size, void* stream);
+/* ff_epipolar_ransac with a hold: hold (B) uint8 on the device, or null (then it IS ff_epipolar_ransac).  Where hold[b] != 0
+ * sample b gets no verdict whatever its hypotheses score: ok = 0, F zero, inliers = 0, candidates = M, candidate rows get status
+ * 4, dist2 +inf on rows, valid and the table are left alone.  The launches and the epoch's increment are the same.  The
+ * homography check sets it where ONE homography explains the pair: F is under-determined there (every [e']x H fits). */
+int ff_epipolar_ransac_hold(const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K,
+                            int min_inliers, int permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids,
+                            int* age, float* F, float* dist2, unsigned char* status, int* inliers, int* candidates,
+                            unsigned char* ok, void* ws, long long ws_size, const unsigned char* hold, void* stream);
+/* Homography check of a video session (csrc/homography.hip): does ONE plane-induced map x' ~ H x explain the rows of a matches
+ * (B,N,4) [x, y, x', y'] / valid (B,N) pair - a planar scene, or a camera that only rotates?  A RANSAC over K homographies from
+ * 4 rows each (the DLT of Hartley & Zisserman, alg. 4.1) in frame-normalised coordinates, scored by the one-sided transfer
+ * error.  Exact as the epipolar check is: fp32, every operation rounded separately, no FMA; tests/homography_ref.py restates all
+ * of it in numpy.  Candidates, normalisation, word(), the elimination and the argmax are those of ff_epipolar_ransac, word for
+ * word, so both checks see the same rows of a session.  Per sample b:
+ *   draws          hypothesis k of epoch e takes 4 distinct ranks by Floyd's algorithm: for j = 0 .. 3, n = M - 4 + j,
+ *                  t = word(seed, e, b, 4 k + j) mod (n + 1), take t unless taken already, else n
+ *   model          the 8 x 9 system with rows 2 j: [x, y, 1, 0, 0, 0, -(x'x), -(x'y), -x'] and 2 j + 1: [0, 0, 0, x, y, 1, -(y'x),
+ *                  -(y'y), -y'] of draw j, eliminated and back-substituted as for ff_epipolar_ransac (free unknown 1).  Then
+ *                  w_j = (h6 x + h7 y) + h8 on the four rows of the sample.  A hypothesis is degenerate and scores 0 if a step
+ *                  meets no pivot > 0, if an unknown is not finite, or if the w_j are not all > 0 or all < 0 (three collinear
+ *                  points, or a map that folds the plane between them); where all are < 0 the nine values are negated (exact),
+ *                  so every model has w > 0 on its sample.  No refit on the inliers
+ *   score          u = (h0 x + h1 y) + h2, v and w alike; num = (u - x' w)^2 + (v - y' w)^2, den = w w; a row is an inlier where
+ *                  w > 0 and num <= t den, t = (float)(threshold^2 s^2) made in double: the transfer error in the second image
+ *                  only.  The best hypothesis has the most inliers, the lowest k among equal counts
+ *   verdict        ok = M >= 4 and count >= min_inliers and 1000 count >= permille M;
+ *                  planar = ok and 1000 count >= planar_permille M
+ * Outputs: Hm (B,3,3) in pixel coordinates of the unpadded frame, (x', y', 1) ~ Hm (x, y, 1): T^-1 Hn T with T = [[s, 0, -cx s],
+ * [0, s, -cy s], [0, 0, 1]], G = Hn T first (G(i,0) = h(i,0) s, G(i,1) = h(i,1) s, G(i,2) = h(i,2) - (G(i,0) cx + G(i,1) cy)), then
+ * Hm(0,j) = G(0,j) / s + cx G(2,j), Hm(1,j) = G(1,j) / s + cy G(2,j), Hm(2,j) = G(2,j); zeros when ok = 0.  dist2 (B,N): the squared
+ * transfer error in px^2 under the best model, (num / den) / s^2 (den = 0: 0 for an inlier, else +inf), +inf where w <= 0, -1 for
+ * no row, +inf for a row with a non-finite value and for every row when ok = 0.  status, inliers, candidates, ok, the side
+ * effects on valid and the table (cull), epoch, ws (ff_homography_ws bytes: the formula of ff_epipolar_ws) and the refusals: as
+ * for ff_epipolar_ransac; planar (B) uint8; planar_permille outside 0 .. 1000 is refused.  Four launches; enqueues only,
+ * allocates nothing, no atomics. */
+int ff_homography_ws(int B, int N, int K);
+int ff_homography_ransac(const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K, int min_inliers,
+                         int permille, int planar_permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids,
+                         int* age, float* Hm, float* dist2, unsigned char* status, int* inliers, int* candidates, unsigned char* ok,
+                         unsigned char* planar, void* ws, long long ws_size, void* stream);
+/* The dense residual of a flow field against the homographies of ff_homography_ransac: out (B,Himg,Wimg) fp32, contiguous,
+ *   out[b,y,x] = dx dx + dy dy, dx = (x + u) - U / Wd, dy = (y + v) - V / Wd, (U, V, Wd) = Hm_b (x, y, 1) each (a x + b y) + c,
+ * in px^2 (correctly rounded divisions, nothing fused): what remains of the flow once the map's motion is removed, the
+ * independently moving foreground under a rotating camera.  +inf where Wd <= 0 (or NaN); -1 over the whole sample where
+ * ok[b] = 0.  x, y: pixel coordinates of the unpadded frame, those of the matches.  flow: u at flow[b ld_b + y ld_row + x ld_col],
+ * v ld_c behind it (strides in elements, so the crop of a padded flow is passed as the view it is).  One launch, one pass, moved
+ * as float4 where the addresses allow.  Refused: B outside 1 .. 65535, Himg outside 1 .. 2^18, Wimg outside 1 .. 2^24, a null
+ * pointer, a negative stride. */
+int ff_homography_residual(const float* flow, long long ld_b, long long ld_c, long long ld_row, long long ld_col, const float* Hm,
+                           const unsigned char* ok, int B, int Himg, int Wimg, float* out, void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
