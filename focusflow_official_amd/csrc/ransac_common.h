@@ -1,8 +1,8 @@
 // What the two RANSAC checks of a video session share (epipolar.hip: fundamental matrices from 8 rows; homography.hip:
-// homographies from 4): which rows are candidates, the frame normalisation, the hash of the draws, the workspace, the
-// compaction launch, the elimination of an 8 x 9 system and the argmax over the hypotheses.  Both checks must see the same rows
-// of a session in the same order, so these are spelled once.  Exact fp32: a file that includes this sets
-// `#pragma clang fp contract(off)` first.
+// homographies from 4), which is everything but the model: which rows are candidates, the frame normalisation, the workspace, the
+// four launches (compaction; draws, elimination of an 8 x 9 system; scoring; argmax, verdict and flags), templates over a Model,
+// and the host function that checks the arguments and enqueues them.  Both checks must see the same rows of a session in the
+// same order, so these are spelled once.  Exact fp32: a file that includes this sets `#pragma clang fp contract(off)` first.
 #pragma once
 #include <climits>
 #include "ff_common.h"
@@ -181,9 +181,192 @@ __device__ __forceinline__ void best_hypothesis(const int* counts, int K, int& b
     }
 }
 
-}  // namespace
+// num / den of a judge; a vanishing den measures nothing: 0 for an inlier (num = 0 too), else +inf
+__device__ __forceinline__ float quotient(float num, float den, bool in) { return den > 0.f ? __fdiv_rn(num, den) : (in ? 0.f : __builtin_inff()); }
 
-#define FF_REQUIRE_RANSAC_SHAPE(name)                                                                                    \
-    FF_REQUIRE(B > 0 && B <= MAX_BATCH, name ": B = %d (1 .. %d samples)", B, MAX_BATCH);                                   \
-    FF_REQUIRE(N >= 1 && N <= MAX_ROWS, name ": N = %d (1 .. %d rows)", N, MAX_ROWS);                                    \
-    FF_REQUIRE(K >= 1 && K <= MAX_HYP, name ": K = %d (1 .. %d hypotheses)", K, MAX_HYP)
+// ---- the three launches behind the compaction, once.  What a check brings is its Model:
+//   SAMPLE                         the rows of a minimal sample (at most 8)
+//   PLANAR                         (host) the check has a second verdict: planar_permille and the `planar` output are required
+//   rows(sys, lane, j, x, y, xp, yp)   what draw j, the normalised row [x, y, x', y'], puts into this thread's 8 x 9 system
+//   accept(good, model, px, py)    behind solve_8x9 (-> good): may refuse the model of the sample (px, py)[0 .. SAMPLE) or rewrite
+//                                  it in place.  -> good
+//   judge(m, p, t, d2) -> inlier   THE expression of the scoring pass and of the final flags; d2: the squared distance of row p
+//                                  to model m in normalised units, +inf where there is none
+//   to_pixels(g, fr, out)          the best model in pixel coordinates from g = m T, T = [[s, 0, -cx s], [0, s, -cy s], [0, 0, 1]]
+
+// one thread per hypothesis: SAMPLE distinct ranks (Floyd), the system, elimination with full pivoting, back-substitution.  The
+// system lives in LDS as [element][thread]: a pivot's row and column are run-time indices, which a register array would answer
+// with scratch, and lane l of a wave reads bank l mod 64 whatever element it asks for
+template <class Model>
+__global__ void __launch_bounds__(WAVE) ransac_hypotheses_kernel(int N, int K, unsigned seed, const int* __restrict__ epoch, Workspace ws) {
+    constexpr int S = Model::SAMPLE;
+    __shared__ float sys[72 * WAVE];
+    __shared__ int perm[9 * WAVE];
+    const int b = blockIdx.y, lane = threadIdx.x, k = blockIdx.x * WAVE + lane;
+    if (k >= K) return;      // (no barrier below: a thread works on its own column of the LDS arrays)
+    const int M = ws.m[b];
+    int* count = ws.counts + (long long)b * K + k;
+    if (M < S) {
+        *count = -1;
+        return;
+    }
+    // the draws: Floyd's algorithm, S distinct ranks below M
+    unsigned h = mix(seed + 0x9e3779b9u);
+    h = mix(h ^ (unsigned)*epoch);
+    h = mix(h ^ (unsigned)b);
+    int pick[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        const int n = M - S + j;
+        int t = (int)(mix(h ^ (unsigned)(S * k + j)) % (unsigned)(n + 1));
+        bool taken = false;
+#pragma unroll
+        for (int i = 0; i < j; ++i) taken |= pick[i] == t;
+        pick[j] = taken ? n : t;
+    }
+    const float* planes = ws.planes + (long long)b * 4 * N;
+    float px[S], py[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        const float x = planes[pick[j]], y = planes[N + pick[j]], xp = planes[2 * N + pick[j]], yp = planes[3 * N + pick[j]];
+        px[j] = x, py[j] = y;
+        Model::rows(sys, lane, j, x, y, xp, yp);
+    }
+    float* model = ws.models + ((long long)b * K + k) * 9;
+    const bool good = Model::accept(solve_8x9(sys, perm, lane, model), model, px, py);
+    *count = good ? 0 : -1;
+}
+
+// one wave per hypothesis: lanes over the candidates, the inlier count by ballot and popcount.  counts in: 0 a model, -1
+// degenerate; out: the inliers (0 for a degenerate hypothesis)
+template <class Model>
+__global__ void __launch_bounds__(SCORE_WAVES* WAVE) ransac_score_kernel(int N, int K, float t, Workspace ws) {
+    const int b = blockIdx.y, lane = threadIdx.x % WAVE, k = blockIdx.x * SCORE_WAVES + threadIdx.x / WAVE;
+    if (k >= K) return;
+    int* count = ws.counts + (long long)b * K + k;
+    const int M = ws.m[b];
+    int inliers = 0;
+    if (*count == 0) {      // (uniform over the wave)
+        const float* model = ws.models + ((long long)b * K + k) * 9;
+        float f[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) f[i] = model[i];
+        const float* planes = ws.planes + (long long)b * 4 * N;
+        for (int r0 = 0; r0 < M; r0 += WAVE) {
+            const int r = r0 + lane;
+            bool in = false;
+            if (r < M) {
+                float d2;
+                in = Model::judge(f, make_float4(planes[r], planes[N + r], planes[2 * N + r], planes[3 * N + r]), t, d2);
+            }
+            inliers += __popcll(__ballot(in));
+        }
+    }
+    if (lane == 0) *count = inliers;
+}
+
+// one block per sample: argmax over K (the lowest k of equal counts), the verdict - none for a sample that `hold` (null: no
+// sample) names -, `planar` (null: the check has none), then per row status, dist2, valid and the culled table; the model; the
+// epoch word
+template <class Model>
+__global__ void __launch_bounds__(BLOCK) ransac_select_kernel(const float4* __restrict__ matches, unsigned char* __restrict__ valid, int N, int K, Frame fr,
+                                                              float t, float s2, int min_inliers, int permille, int planar_permille, int cull,
+                                                              float2* __restrict__ pos, long long* __restrict__ ids, int* __restrict__ age,
+                                                              float* __restrict__ model_out, float* __restrict__ dist2,
+                                                              unsigned char* __restrict__ status, int* __restrict__ inliers, int* __restrict__ candidates,
+                                                              unsigned char* __restrict__ ok_out, unsigned char* __restrict__ planar_out,
+                                                              int* __restrict__ epoch, const unsigned char* __restrict__ hold, Workspace ws) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int bc, bk;
+    best_hypothesis(ws.counts + (long long)b * K, K, bc, bk);
+    const int M = ws.m[b];
+    const bool held = hold && hold[b];      // (ff_epipolar_ransac_hold: this sample gets no verdict, whatever its hypotheses scored)
+    const bool ok = !held && M >= Model::SAMPLE && bc >= min_inliers && 1000ll * bc >= (long long)permille * M;
+    float f[9];
+    const float* model = ws.models + ((long long)b * K + bk) * 9;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f[i] = ok ? model[i] : 0.f;
+    for (int n = tid; n < N; n += BLOCK) {
+        const long long r = (long long)b * N + n;
+        const float4 m = matches[r];
+        float d = -1.f;
+        unsigned char st = 0;
+        if (!(m.x < 0.f)) {      // a row: a no-row holds x = -1
+            const bool cand = candidate(m, valid[r]);
+            st = cand ? 4 : 2;
+            d = __builtin_inff();
+            if (ok && finite4(m)) {
+                float d2;
+                const bool in = Model::judge(f, normalise(m, fr), t, d2);
+                d = __fdiv_rn(d2, s2);
+                if (cand) st = in ? 1 : 3;
+            }
+        }
+        dist2[r] = d;
+        status[r] = st;
+        if (st == 3) {
+            valid[r] = 0;
+            if (cull && pos) {
+                pos[r] = make_float2(-1.f, -1.f);
+                ids[r] = -1;
+                age[r] = 0;
+            }
+        }
+    }
+    if (tid == 0) {
+        inliers[b] = ok ? bc : 0;
+        candidates[b] = M;
+        ok_out[b] = ok;
+        if (planar_out) planar_out[b] = ok && 1000ll * bc >= (long long)planar_permille * M;
+        float g[9];      // (all zero without a verdict, and so is the model)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            g[3 * i] = f[3 * i] * fr.s;
+            g[3 * i + 1] = f[3 * i + 1] * fr.s;
+            g[3 * i + 2] = f[3 * i + 2] - (g[3 * i] * fr.cx + g[3 * i + 1] * fr.cy);
+        }
+        Model::to_pixels(g, fr, model_out + b * 9);
+        if (b == 0) *epoch = *epoch + 1;      // (the hypotheses of this call read it in an earlier launch)
+    }
+}
+
+inline int ws_or_0(int B, int N, int K) {      // ff_*_ws: 0 for a shape that the check refuses
+    if (B <= 0 || B > MAX_BATCH || N < 1 || N > MAX_ROWS || K < 1 || K > MAX_HYP) return 0;
+    return (int)ws_bytes(B, N, K);
+}
+
+// The host side of a check: its argument checks under the entry's `name`, then the four launches on `stream`.  A Model without
+// PLANAR passes planar_permille 0 and planar null.
+template <class Model>
+int ransac(const char* name, const float* matches, unsigned char* valid, int B, int N, int H, int W, float threshold, int K, int min_inliers, int permille,
+           int planar_permille, unsigned int seed, int* epoch, int cull, float* pos, long long* ids, int* age, float* model, float* dist2,
+           unsigned char* status, int* inliers, int* candidates, unsigned char* ok, unsigned char* planar, void* ws, long long ws_size,
+           const unsigned char* hold, void* stream) {
+    FF_REQUIRE(B > 0 && B <= MAX_BATCH, "%s: B = %d (1 .. %d samples)", name, B, MAX_BATCH);
+    FF_REQUIRE(N >= 1 && N <= MAX_ROWS, "%s: N = %d (1 .. %d rows)", name, N, MAX_ROWS);
+    FF_REQUIRE(K >= 1 && K <= MAX_HYP, "%s: K = %d (1 .. %d hypotheses)", name, K, MAX_HYP);
+    FF_REQUIRE(H > 0 && W > 0 && H <= (1 << 24) && W <= (1 << 24), "%s: H = %d, W = %d (1 .. 2^24: positions are fp32)", name, H, W);
+    FF_REQUIRE(threshold >= 0.f && threshold < __builtin_inff(), "%s: threshold = %g (>= 0 and finite, no NaN)", name, (double)threshold);
+    FF_REQUIRE(min_inliers >= 1, "%s: min_inliers = %d (at least 1: a degenerate hypothesis scores 0)", name, min_inliers);
+    FF_REQUIRE(permille >= 0 && permille <= 1000, "%s: permille = %d (0 .. 1000)", name, permille);
+    FF_REQUIRE(planar_permille >= 0 && planar_permille <= 1000, "%s: planar_permille = %d (0 .. 1000)", name, planar_permille);
+    FF_REQUIRE(matches && valid && epoch && model && dist2 && status && inliers && candidates && ok && (planar || !Model::PLANAR) && ws, "%s: null pointer",
+               name);
+    FF_REQUIRE((pos && ids && age) || (!pos && !ids && !age), "%s: a track table is pos, ids and age: all three or none", name);
+    FF_REQUIRE(((size_t)matches & 15) == 0 && ((size_t)pos & 7) == 0, "%s: matches must be 16-byte aligned, pos 8-byte aligned", name);
+    FF_REQUIRE(((size_t)ws & 15) == 0 && ws_size >= (long long)ws_bytes(B, N, K), "%s: ws must be 16-byte aligned and hold %lld bytes, got %lld", name,
+               (long long)ws_bytes(B, N, K), ws_size);
+    const Frame fr = frame_of(H, W);
+    const float t = (float)((double)threshold * (double)threshold * (double)fr.s * (double)fr.s), s2 = (float)((double)fr.s * (double)fr.s);
+    const Workspace w = carve(ws, B, N, K);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const float4* m4 = reinterpret_cast<const float4*>(matches);
+    epi_compact_kernel<<<B, BLOCK, 0, s>>>(m4, valid, N, fr, w);
+    ransac_hypotheses_kernel<Model><<<dim3((K + WAVE - 1) / WAVE, B), WAVE, 0, s>>>(N, K, seed, epoch, w);
+    ransac_score_kernel<Model><<<dim3((K + SCORE_WAVES - 1) / SCORE_WAVES, B), SCORE_WAVES * WAVE, 0, s>>>(N, K, t, w);
+    ransac_select_kernel<Model><<<B, BLOCK, 0, s>>>(m4, valid, N, K, fr, t, s2, min_inliers, permille, planar_permille, cull, reinterpret_cast<float2*>(pos),
+                                                    ids, age, model, dist2, status, inliers, candidates, ok, planar, epoch, hold, w);
+    return ff::check_launch(name);
+}
+
+}  // namespace

@@ -54,6 +54,7 @@ where it does (F is under-determined there), and with Homography.dense writes th
     res.hom.status, res.hom.dist2            # per row of res.matches, as res.epi's; the squared transfer error in px^2
     res.hom.residual                         # dense=True: (B,H,W) fp32 px^2, -1 without a verdict; else None
 """
+from operator import itemgetter
 from typing import NamedTuple, Optional
 
 import torch
@@ -75,6 +76,21 @@ class FBCheck(NamedTuple):
     warm: bool = True
 
 
+def as_fb(fb) -> Optional[FBCheck]:
+    """None / False -> None, True -> the defaults, an FBCheck -> itself, checked; anything else is a ValueError."""
+    if fb is None or fb is False:
+        return None
+    if fb is True:
+        return FBCheck()
+    if not isinstance(fb, FBCheck):
+        raise ValueError(f"fb: True or a frames.FBCheck(alpha, beta, iters, warm) expected, got {type(fb).__name__}")
+    if not (fb.alpha >= 0 and fb.beta >= 0):
+        raise ValueError(f"fb: alpha={fb.alpha}, beta={fb.beta}: both >= 0 (and no NaN)")
+    if fb.iters is not None and int(fb.iters) < 1:
+        raise ValueError(f"fb: iters={fb.iters}: None (the session's raft_iters) or at least 1")
+    return fb
+
+
 class FBResult(NamedTuple):
     """What a pair adds to a FrameResult in a session with fb=: the backward flow as the (B,2,H,W) unpadded view, the dense
     squared round-trip error (B,1,H,W) fp32 and occlusion map (B,1,H,W) uint8, and per row of `matches` the error (B,N) fp32 and
@@ -93,30 +109,26 @@ class FrameResult(tuple):
     items it always had, so a caller that unpacks or walks them goes on working, and `.tracks` and `.fb` are None.  A session with
     epipolar= gets the shape it would have without, plus a last item `epi` (a geometry.EpiResult): Epi-, TrackedEpi-, CheckedEpi-
     and TrackedCheckedEpiFrameResult; `.epi` is None in the four shapes without.  A session with homography= likewise gets the
-    shape it would have without, plus a last item `hom` (a geometry.HomResult): each of the eight has a generated subclass whose
-    name puts Hom before FrameResult (HomFrameResult .. TrackedCheckedEpiHomFrameResult); `.hom` is None in the eight without.  All
-    sixteen behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
+    shape it would have without, plus a last item `hom` (a geometry.HomResult): each of the eight has a subclass whose name
+    puts Hom before FrameResult (HomFrameResult .. TrackedCheckedEpiHomFrameResult); `.hom` is None in the eight without.  The
+    fifteen subclasses are generated from one table (_OPTIONAL), and all sixteen behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
     __slots__ = ()
     _fields = ("flow_low", "flow_up", "matches", "valid", "count")
 
     def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None, fb: Optional[FBResult] = None,
                 epi: Optional[EpiResult] = None, hom: Optional[HomResult] = None):
-        extras = tuple(x for x in (tracks, fb, epi, hom) if x is not None)
-        shape = _SHAPES[(tracks is not None, fb is not None, epi is not None, hom is not None)]
-        return tuple.__new__(shape, (flow_low, flow_up, matches, valid, count) + extras)
+        extras = {f: x for f, x in zip(_OPTIONAL_FIELDS, (tracks, fb, epi, hom)) if x is not None}
+        return tuple.__new__(_SHAPES[tuple(extras)], (flow_low, flow_up, matches, valid, count, *extras.values()))
 
-    flow_low = property(lambda self: self[0])
-    flow_up = property(lambda self: self[1])
-    matches = property(lambda self: self[2])
-    valid = property(lambda self: self[3])
-    count = property(lambda self: self[4])
-    tracks = property(lambda self: None)
-    fb = property(lambda self: None)
-    epi = property(lambda self: None)
-    hom = property(lambda self: None)
+    flow_low = property(itemgetter(0))
+    flow_up = property(itemgetter(1))
+    matches = property(itemgetter(2))
+    valid = property(itemgetter(3))
+    count = property(itemgetter(4))
+    tracks = fb = epi = hom = property(lambda self: None)      # (a shape that has the item answers with it: _shape)
 
     def __getnewargs__(self):      # (copy, deepcopy and pickle rebuild through __new__, item by item)
-        return tuple(self[:5]) + (self.tracks, self.fb, self.epi, self.hom)
+        return tuple(self[:5]) + tuple(getattr(self, f) for f in _OPTIONAL_FIELDS)
 
     @classmethod
     def _make(cls, iterable):
@@ -127,7 +139,7 @@ class FrameResult(tuple):
             return FrameResult(*items)      # (too few or too many: the TypeError of __new__)
         extras = {}
         for x in items[5:]:
-            name = "fb" if isinstance(x, FBResult) else "epi" if isinstance(x, EpiResult) else "hom" if isinstance(x, HomResult) else "tracks"
+            name = next((f for f, _, kind in _OPTIONAL if isinstance(x, kind)), "tracks")
             if name in extras:
                 raise TypeError(f"FrameResult._make: two items for `{name}`")
             extras[name] = x
@@ -137,7 +149,7 @@ class FrameResult(tuple):
         return dict(zip(self._fields, self))
 
     def _replace(self, **kwargs):
-        unknown = set(kwargs) - set(FrameResult._fields + ("tracks", "fb", "epi", "hom"))
+        unknown = set(kwargs) - set(FrameResult._fields + _OPTIONAL_FIELDS)
         if unknown:
             raise ValueError(f"Got unexpected field names: {sorted(unknown)!r}")
         return FrameResult(**{**self._asdict(), **kwargs})
@@ -146,77 +158,32 @@ class FrameResult(tuple):
         return "FrameResult(" + ", ".join(f"{n}={v!r}" for n, v in zip(self._fields, self)) + ")"
 
 
-class TrackedFrameResult(FrameResult):
-    """A FrameResult of a session with tracks: six items, the last one `tracks`.  Made by FrameResult(..., tracks=...)."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("tracks",)
-    tracks = property(lambda self: self[5])
+# The optional items behind the fifth, in their order: the field, what its presence puts into the class name, the type that
+# identifies it in _make.  The next check's result is one more row (and one more keyword of __new__).
+_OPTIONAL = (("tracks", "Tracked", TrackResult), ("fb", "Checked", FBResult), ("epi", "Epi", EpiResult), ("hom", "Hom", HomResult))
+_OPTIONAL_FIELDS = tuple(row[0] for row in _OPTIONAL)
 
 
-class CheckedFrameResult(FrameResult):
-    """A FrameResult of a session with fb= and no tracks: six items, the last one `fb`.  Made by FrameResult(..., fb=...)."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("fb",)
-    fb = property(lambda self: self[5])
+def _shape(rows):
+    """The class of a FrameResult with the optional items `rows` (a non-empty selection from _OPTIONAL, in its order).  A shape
+    with `hom` is a subclass of the shape without, so `tracks`, `fb` and `epi` stay where they are; every other one is a direct
+    subclass of FrameResult."""
+    fields, name = tuple(r[0] for r in rows), "".join(r[1] for r in rows) + "FrameResult"
+    base = _SHAPES[fields[:-1]] if fields[-1] == "hom" else FrameResult
+    body = {"__slots__": (), "__module__": __name__, "__qualname__": name, "_fields": FrameResult._fields + fields,
+            "__doc__": f"A FrameResult of a session with {', '.join(fields)}: {5 + len(fields)} items, those last.  Made by "
+                       f"FrameResult(..., {', '.join(f + '=...' for f in fields)})."}
+    body.update((f, property(itemgetter(5 + i))) for i, f in enumerate(fields))
+    return type(name, (base,), body)
 
 
-class TrackedCheckedFrameResult(FrameResult):
-    """A FrameResult of a session with tracks and fb=: seven items, `tracks` and `fb` last.  Made by FrameResult(..., tracks=..., fb=...)."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("tracks", "fb")
-    tracks = property(lambda self: self[5])
-    fb = property(lambda self: self[6])
-
-
-class EpiFrameResult(FrameResult):
-    """A FrameResult of a session with epipolar=, without tracks and fb=: six items, the last one `epi`.  Made by FrameResult(..., epi=...)."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("epi",)
-    epi = property(lambda self: self[5])
-
-
-class TrackedEpiFrameResult(FrameResult):
-    """A FrameResult of a session with tracks and epipolar=: seven items, `tracks` and `epi` last."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("tracks", "epi")
-    tracks = property(lambda self: self[5])
-    epi = property(lambda self: self[6])
-
-
-class CheckedEpiFrameResult(FrameResult):
-    """A FrameResult of a session with fb= and epipolar=, without tracks: seven items, `fb` and `epi` last."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("fb", "epi")
-    fb = property(lambda self: self[5])
-    epi = property(lambda self: self[6])
-
-
-class TrackedCheckedEpiFrameResult(FrameResult):
-    """A FrameResult of a session with tracks, fb= and epipolar=: eight items, `tracks`, `fb` and `epi` last."""
-    __slots__ = ()
-    _fields = FrameResult._fields + ("tracks", "fb", "epi")
-    tracks = property(lambda self: self[5])
-    fb = property(lambda self: self[6])
-    epi = property(lambda self: self[7])
-
-
-def _with_hom(base):
-    """The shape of `base` plus a last item `hom`: a subclass of it, so `tracks`, `fb` and `epi` stay where they are."""
-    name = base.__name__.replace("FrameResult", "HomFrameResult")
-    return type(name, (base,), {"__slots__": (), "__module__": __name__, "__qualname__": name, "_fields": base._fields + ("hom",),
-                                "hom": property(lambda self: self[-1]),
-                                "__doc__": f"A {base.__name__} of a session with homography=: {len(base._fields) + 1} items, the last one `hom`.  "
-                                           "Made by FrameResult(..., hom=...)."})
-
-
-# (tracks, fb, epi, hom) present -> the shape; the eight with hom are generated (pickle finds them in this module by name)
-_SHAPES = {(False, False, False, False): FrameResult, (True, False, False, False): TrackedFrameResult, (False, True, False, False): CheckedFrameResult,
-           (True, True, False, False): TrackedCheckedFrameResult, (False, False, True, False): EpiFrameResult,
-           (True, False, True, False): TrackedEpiFrameResult, (False, True, True, False): CheckedEpiFrameResult,
-           (True, True, True, False): TrackedCheckedEpiFrameResult}
-for _key, _base in list(_SHAPES.items()):
-    _SHAPES[_key[:3] + (True,)] = globals()[_base.__name__.replace("FrameResult", "HomFrameResult")] = _with_hom(_base)
-del _key, _base
+# the items present -> the shape.  All sixteen are module attributes: pickle finds them by name
+_SHAPES = {(): FrameResult}
+for _n in range(1, 2 ** len(_OPTIONAL)):      # (`hom` is the highest bit: a shape without it is made before the one with it)
+    _rows = [row for _i, row in enumerate(_OPTIONAL) if _n >> _i & 1]
+    _cls = _shape(_rows)
+    _SHAPES[_cls._fields[5:]] = globals()[_cls.__name__] = _cls
+del _n, _rows, _cls
 
 
 class FrameSequence:
@@ -301,21 +268,12 @@ class FrameSequence:
             self._slots = keypoints.max_corners if tracks is True else int(tracks)
             if not 1 <= self._slots <= MAX_SLOTS or keypoints.max_corners > MAX_SLOTS:
                 raise ValueError(f"tracks: {self._slots} slots for a detector of max_corners={keypoints.max_corners}: both 1 .. {MAX_SLOTS}")
-        self.fb = None      # the FBCheck of the session; None: no forward-backward check
-        if fb is not None and fb is not False:
-            self.fb = FBCheck() if fb is True else fb
-            if not isinstance(self.fb, FBCheck):
-                raise ValueError(f"fb: True or a frames.FBCheck(alpha, beta, iters, warm) expected, got {type(fb).__name__}")
-            if not (self.fb.alpha >= 0 and self.fb.beta >= 0):
-                raise ValueError(f"fb: alpha={self.fb.alpha}, beta={self.fb.beta}: both >= 0 (and no NaN)")
-            if self.fb.iters is not None and int(self.fb.iters) < 1:
-                raise ValueError(f"fb: iters={self.fb.iters}: None (the session's raft_iters) or at least 1")
+        self.fb = as_fb(fb)      # the FBCheck of the session; None: no forward-backward check
         self.epipolar = as_epipolar(epipolar)      # the geometry.Epipolar of the session; None: no epipolar check
-        if self.epipolar is not None and keypoints is None:
-            raise ValueError("epipolar: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
         self.homography = as_homography(homography)      # the geometry.Homography of the session; None: no homography check
-        if self.homography is not None and keypoints is None:
-            raise ValueError("homography: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
+        for word, config in (("epipolar", self.epipolar), ("homography", self.homography)):
+            if config is not None and keypoints is None:
+                raise ValueError(f"{word}: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
         self._reads_mask = getattr(model, "mask_modal", None) is not None
         self._require_eval()
         self._key = None
@@ -432,14 +390,15 @@ class FrameSequence:
             if self.fb.warm:
                 self._fb_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
                 ops.negate(self._fb_init, self._fb_init)      # (makes the constant negate() reads now, not inside a capture)
+        rows = self._slots or (self.keypoints.max_corners if self.keypoints is not None else 0)      # N of the matches the checks judge
         if self.epipolar is not None:
             self._epi = EpipolarCheck(self.epipolar)
-            self._epi.prepare(b, self._slots or self.keypoints.max_corners, device)      # (now, not inside a capture)
+            self._epi.prepare(b, rows, device)      # (now, not inside a capture)
         if self.homography is not None:
             self._hom = HomographyCheck(self.homography)
-            self._hom.prepare(b, self._slots or self.keypoints.max_corners, device, h, w)
+            self._hom.prepare(b, rows, device, h, w)
             if not self.homography.cull:
-                self._hom_valid = torch.zeros((b, self._slots or self.keypoints.max_corners), dtype=torch.uint8, device=device)
+                self._hom_valid = torch.zeros((b, rows), dtype=torch.uint8, device=device)
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -475,8 +434,8 @@ class FrameSequence:
             count, tracks = live, TrackResult(ids, age, born)
         elif det is not None:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
-        fb = self._check(flow_low, flow_up, matches, valid) if self.fb is not None else None
-        table = None if tb is None else (tb.pos, tb.ids, tb.age)
+        table = None if tb is None else (tb.pos, tb.ids, tb.age)      # what the three checks cull
+        fb = self._check(flow_low, flow_up, matches, valid, table) if self.fb is not None else None
         flow_up = flow_up[:, :, top:top + h, left:left + w]
         epi = hom = None
         if self._hom is not None:      # behind fb, before epipolar: both see the same candidates unless Homography.cull
@@ -488,7 +447,7 @@ class FrameSequence:
             epi = self._epi(matches, valid, h, w, table=table, hold=hold)
         return FrameResult(flow_low, flow_up, matches, valid, count, tracks, fb, epi, hom)
 
-    def _check(self, flow_low, flow_up, matches, valid):
+    def _check(self, flow_low, flow_up, matches, valid, table):
         """The forward-backward part of a step, behind the advance / the matches: the backward pair's mask, the backward flow's
         start, the backward flow, the dense check, the point check (which clears `valid` and culls the table).  -> FBResult."""
         b, h, w = self._bhw
@@ -524,8 +483,7 @@ class FrameSequence:
         err2, occluded = ops.fb_dense(flow_up, flow_bw, left, top, h, w, fb.alpha, fb.beta)
         point_err2 = status = None
         if matches is not None:
-            point_err2, status = ops.fb_matches(matches, valid, flow_bw, left, top, h, w, fb.alpha, fb.beta,
-                                                table=None if tb is None else (tb.pos, tb.ids, tb.age))
+            point_err2, status = ops.fb_matches(matches, valid, flow_bw, left, top, h, w, fb.alpha, fb.beta, table=table)
         return FBResult(flow_bw[:, :, top:top + h, left:left + w], err2, occluded, point_err2, status)
 
     def _capture(self, warmup=3):

@@ -39,7 +39,40 @@ import torch
 
 from . import ops
 
-MAX_HYPOTHESES = 4096      # csrc/epipolar.hip
+MAX_HYPOTHESES = 4096      # csrc/ransac_common.h
+
+
+def _validated(config, ratios=("min_ratio",)):
+    """-> config, or a ValueError that names the check (the configuration's class name in lower case) and the field."""
+    word = type(config).__name__.lower()
+    if not (isinstance(config.threshold, (int, float)) and 0 <= config.threshold < float("inf")):
+        raise ValueError(f"{word}: threshold={config.threshold}: a finite number of pixels >= 0 (and no NaN)")
+    if not (isinstance(config.hypotheses, int) and 1 <= config.hypotheses <= MAX_HYPOTHESES):
+        raise ValueError(f"{word}: hypotheses={config.hypotheses}: 1 .. {MAX_HYPOTHESES}")
+    if not (isinstance(config.min_inliers, int) and config.min_inliers >= 1):
+        raise ValueError(f"{word}: min_inliers={config.min_inliers}: at least 1")
+    for name in ratios:
+        ratio = getattr(config, name)
+        if not (isinstance(ratio, (int, float)) and 0 <= ratio <= 1):
+            raise ValueError(f"{word}: {name}={ratio}: 0 .. 1 (and no NaN)")
+    if not isinstance(config.seed, int):
+        raise ValueError(f"{word}: seed={config.seed!r}: an integer")
+    return config
+
+
+def _permille(ratio):
+    return int(round(1000 * ratio))
+
+
+def _as_config(value, cls):
+    """None / False -> None, True -> the defaults, a `cls` -> itself, validated; anything else is a ValueError."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return cls()
+    if not isinstance(value, cls):
+        raise ValueError(f"{cls.__name__.lower()}: True or a geometry.{cls.__name__}({', '.join(cls._fields)}) expected, got {type(value).__name__}")
+    return value.validated()
 
 
 class Epipolar(NamedTuple):
@@ -56,21 +89,9 @@ class Epipolar(NamedTuple):
 
     def validated(self):
         """-> self, or a ValueError that names `epipolar` and the field."""
-        if not (isinstance(self.threshold, (int, float)) and 0 <= self.threshold < float("inf")):
-            raise ValueError(f"epipolar: threshold={self.threshold}: a finite number of pixels >= 0 (and no NaN)")
-        if not (isinstance(self.hypotheses, int) and 1 <= self.hypotheses <= MAX_HYPOTHESES):
-            raise ValueError(f"epipolar: hypotheses={self.hypotheses}: 1 .. {MAX_HYPOTHESES}")
-        if not (isinstance(self.min_inliers, int) and self.min_inliers >= 1):
-            raise ValueError(f"epipolar: min_inliers={self.min_inliers}: at least 1")
-        if not (isinstance(self.min_ratio, (int, float)) and 0 <= self.min_ratio <= 1):
-            raise ValueError(f"epipolar: min_ratio={self.min_ratio}: 0 .. 1 (and no NaN)")
-        if not isinstance(self.seed, int):
-            raise ValueError(f"epipolar: seed={self.seed!r}: an integer")
-        return self
+        return _validated(self)
 
-    @property
-    def permille(self):
-        return int(round(1000 * self.min_ratio))
+    permille = property(lambda self: _permille(self.min_ratio))
 
 
 class EpiResult(NamedTuple):
@@ -87,24 +108,20 @@ class EpiResult(NamedTuple):
 
 def as_epipolar(epipolar) -> Optional[Epipolar]:
     """None / False -> None, True -> the defaults, an Epipolar -> itself, validated; anything else is a ValueError."""
-    if epipolar is None or epipolar is False:
-        return None
-    if epipolar is True:
-        return Epipolar()
-    if not isinstance(epipolar, Epipolar):
-        raise ValueError(f"epipolar: True or a geometry.Epipolar(threshold, hypotheses, min_inliers, min_ratio, cull, seed) expected, "
-                         f"got {type(epipolar).__name__}")
-    return epipolar.validated()
+    return _as_config(epipolar, Epipolar)
 
 
-class EpipolarCheck:
-    """ops.epipolar_ransac with the state it needs between calls: the epoch word (one int32 on the device, so that every call,
-    a replay of a captured one too, draws anew) and, per shape, the workspace and the outputs.  Enqueues only."""
+class _RansacCheck:
+    """What EpipolarCheck and HomographyCheck keep between calls: the configuration, the epoch word (one int32 on the device, so
+    that every call, a replay of a captured one too, draws anew) and, per shape, the workspace and the outputs."""
+    _config = None      # the check's NamedTuple; its name in lower case opens the messages and names ops.<name>_ws
+    _per_sample = (torch.int32, torch.int32, torch.uint8)      # dtypes of the (B) outputs between the model and status, dist2
 
     def __init__(self, config=True):
-        self.config = as_epipolar(config)
+        cls, a = self._config.__name__, "an" if self._config.__name__[0] in "AEIOU" else "a"
+        self.config = _as_config(config, self._config)
         if self.config is None:
-            raise ValueError("epipolar: an EpipolarCheck needs a configuration: True or an Epipolar(...)")
+            raise ValueError(f"{cls.lower()}: {a} {type(self).__name__} needs a configuration: True or {a} {cls}(...)")
         self.epoch = None      # the int32 word on the device; made by the first call
         self._key = self._ws = self._out = None
 
@@ -115,20 +132,30 @@ class EpipolarCheck:
         if key != self._key:
             if self.epoch is None or self.epoch.device != device:
                 self.epoch = torch.zeros((), dtype=torch.int32, device=device)
-            self._ws = torch.empty(max(ops.epipolar_ws(b, n, self.config.hypotheses), 16), dtype=torch.uint8, device=device)
-            self._out = (torch.empty((b, 3, 3), dtype=torch.float32, device=device), torch.empty((b,), dtype=torch.int32, device=device),
-                         torch.empty((b,), dtype=torch.int32, device=device), torch.empty((b,), dtype=torch.uint8, device=device),
+            ws_bytes = getattr(ops, self._config.__name__.lower() + "_ws")
+            self._ws = torch.empty(max(ws_bytes(b, n, self.config.hypotheses), 16), dtype=torch.uint8, device=device)
+            self._out = (torch.empty((b, 3, 3), dtype=torch.float32, device=device),
+                         *(torch.empty((b,), dtype=dtype, device=device) for dtype in self._per_sample),
                          torch.empty((b, n), dtype=torch.uint8, device=device), torch.empty((b, n), dtype=torch.float32, device=device))
             self._key = key
         return self._ws, self._out
+
+    def _buffers(self, matches, *frame):
+        """prepare() for the shape of `matches`; (None, None) where it is no 3-D device tensor: the wrapper then names what is wrong."""
+        if isinstance(matches, torch.Tensor) and matches.is_cuda and matches.dim() == 3:
+            return self.prepare(matches.shape[0], matches.shape[1], matches.device, *frame)
+        return None, None
+
+
+class EpipolarCheck(_RansacCheck):
+    """ops.epipolar_ransac with the state it needs between calls (the epoch word, the workspace, the outputs).  Enqueues only."""
+    _config = Epipolar
 
     def __call__(self, matches, valid, h, w, table=None, hold=None) -> EpiResult:
         """matches (B,N,4) fp32, valid (B,N) uint8 (updated in place), the frame's h and w, table: None or (pos, ids, age), hold:
         None or (B) uint8, samples that get no verdict (HomResult.planar)."""
         c = self.config
-        ws = out = None
-        if isinstance(matches, torch.Tensor) and matches.is_cuda and matches.dim() == 3:      # (else the wrapper names what is wrong)
-            ws, out = self.prepare(matches.shape[0], matches.shape[1], matches.device)
+        ws, out = self._buffers(matches)
         return EpiResult(*ops.epipolar_ransac(matches, valid, h, w, c.threshold, c.hypotheses, c.min_inliers, c.permille, c.seed, self.epoch,
                                               table=table, cull=c.cull, out=out, ws=ws, hold=hold))
 
@@ -156,27 +183,10 @@ class Homography(NamedTuple):
 
     def validated(self):
         """-> self, or a ValueError that names `homography` and the field."""
-        if not (isinstance(self.threshold, (int, float)) and 0 <= self.threshold < float("inf")):
-            raise ValueError(f"homography: threshold={self.threshold}: a finite number of pixels >= 0 (and no NaN)")
-        if not (isinstance(self.hypotheses, int) and 1 <= self.hypotheses <= MAX_HYPOTHESES):
-            raise ValueError(f"homography: hypotheses={self.hypotheses}: 1 .. {MAX_HYPOTHESES}")
-        if not (isinstance(self.min_inliers, int) and self.min_inliers >= 1):
-            raise ValueError(f"homography: min_inliers={self.min_inliers}: at least 1")
-        if not (isinstance(self.min_ratio, (int, float)) and 0 <= self.min_ratio <= 1):
-            raise ValueError(f"homography: min_ratio={self.min_ratio}: 0 .. 1 (and no NaN)")
-        if not (isinstance(self.planar_ratio, (int, float)) and 0 <= self.planar_ratio <= 1):
-            raise ValueError(f"homography: planar_ratio={self.planar_ratio}: 0 .. 1 (and no NaN)")
-        if not isinstance(self.seed, int):
-            raise ValueError(f"homography: seed={self.seed!r}: an integer")
-        return self
+        return _validated(self, ("min_ratio", "planar_ratio"))
 
-    @property
-    def permille(self):
-        return int(round(1000 * self.min_ratio))
-
-    @property
-    def planar_permille(self):
-        return int(round(1000 * self.planar_ratio))
+    permille = property(lambda self: _permille(self.min_ratio))
+    planar_permille = property(lambda self: _permille(self.planar_ratio))
 
 
 class HomResult(NamedTuple):
@@ -195,42 +205,23 @@ class HomResult(NamedTuple):
 
 def as_homography(homography) -> Optional[Homography]:
     """None / False -> None, True -> the defaults, a Homography -> itself, validated; anything else is a ValueError."""
-    if homography is None or homography is False:
-        return None
-    if homography is True:
-        return Homography()
-    if not isinstance(homography, Homography):
-        raise ValueError(f"homography: True or a geometry.Homography({', '.join(Homography._fields)}) expected, got {type(homography).__name__}")
-    return homography.validated()
+    return _as_config(homography, Homography)
 
 
-class HomographyCheck:
+class HomographyCheck(_RansacCheck):
     """ops.homography_ransac (and, with Homography.dense, ops.homography_residual) with the state it needs between calls: an
-    epoch word of its own and, per shape, the workspace and the outputs.  Enqueues only."""
-
-    def __init__(self, config=True):
-        self.config = as_homography(config)
-        if self.config is None:
-            raise ValueError("homography: a HomographyCheck needs a configuration: True or a Homography(...)")
-        self.epoch = None      # the int32 word on the device; made by the first call
-        self._key = self._ws = self._out = self._residual = None
+    epoch word of its own, the workspace, the outputs and the dense residual.  Enqueues only."""
+    _config = Homography
+    _per_sample = _RansacCheck._per_sample + (torch.uint8,)      # planar
+    _residual = None
 
     def prepare(self, b, n, device, h=None, w=None):
-        """The epoch word, the workspace and the outputs for (B, N) - and, with dense, the residual of an h x w frame - on
-        `device`, made once per shape: a session asks for them before it captures.  -> (ws, out)"""
-        key = (b, n, device)
-        if key != self._key:
-            if self.epoch is None or self.epoch.device != device:
-                self.epoch = torch.zeros((), dtype=torch.int32, device=device)
-            self._ws = torch.empty(max(ops.homography_ws(b, n, self.config.hypotheses), 16), dtype=torch.uint8, device=device)
-            self._out = (torch.empty((b, 3, 3), dtype=torch.float32, device=device), torch.empty((b,), dtype=torch.int32, device=device),
-                         torch.empty((b,), dtype=torch.int32, device=device), torch.empty((b,), dtype=torch.uint8, device=device),
-                         torch.empty((b,), dtype=torch.uint8, device=device), torch.empty((b, n), dtype=torch.uint8, device=device),
-                         torch.empty((b, n), dtype=torch.float32, device=device))
-            self._key, self._residual = key, None
+        """As every check's - and, with dense, the residual of an h x w frame.  -> (ws, out)"""
+        if (b, n, device) != self._key:
+            self._residual = None
         if self.config.dense and h is not None and (self._residual is None or tuple(self._residual.shape) != (b, h, w)):
             self._residual = torch.empty((b, h, w), dtype=torch.float32, device=device)
-        return self._ws, self._out
+        return super().prepare(b, n, device)
 
     def __call__(self, matches, valid, h, w, table=None, flow=None) -> HomResult:
         """matches (B,N,4) fp32, valid (B,N) uint8 (updated in place), the frame's h and w, table: None or (pos, ids, age); flow:
@@ -238,9 +229,7 @@ class HomographyCheck:
         c = self.config
         if c.dense and flow is None:
             raise ValueError("homography: dense=True needs the pair's flow: check(matches, valid, h, w, flow=flow_up)")
-        ws = out = None
-        if isinstance(matches, torch.Tensor) and matches.is_cuda and matches.dim() == 3:      # (else the wrapper names what is wrong)
-            ws, out = self.prepare(matches.shape[0], matches.shape[1], matches.device, h if c.dense else None, w)
+        ws, out = self._buffers(matches, h if c.dense else None, w)
         res = ops.homography_ransac(matches, valid, h, w, c.threshold, c.hypotheses, c.min_inliers, c.permille, c.planar_permille, c.seed, self.epoch,
                                     table=table, cull=c.cull, out=out, ws=ws)
         residual = ops.homography_residual(flow, res[0], res[3], out=self._residual) if c.dense else None

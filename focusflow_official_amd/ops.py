@@ -1147,6 +1147,27 @@ def _track_table(name: str, pos: Tensor, ids: Tensor, age: Optional[Tensor] = No
     return b, n
 
 
+def _match_rows(name: str, matches: Tensor, valid: Tensor, table):
+    """What fb_matches, epipolar_ransac and homography_ransac ask of a matches / valid pair and of table: None or the (pos, ids,
+    age) of a track table whose slots are the rows.  -> (B, N, device, pos, ids, age)"""
+    _require_device(matches, name, "matches", (torch.float32,))
+    _require_device(valid, name, "valid", (torch.uint8,))
+    if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
+        raise _hip.FocusFlowHipError(f"{name}: matches must be contiguous (B,N,4), got {tuple(matches.shape)} strides {matches.stride()}")
+    b, n, _ = matches.shape
+    dev = matches.device
+    if tuple(valid.shape) != (b, n) or not valid.is_contiguous() or valid.device != dev:
+        raise _hip.FocusFlowHipError(f"{name}: valid must be contiguous {(b, n)} on {dev}, got {tuple(valid.shape)} strides {valid.stride()} on {valid.device}")
+    pos = ids = age = None
+    if table is not None:
+        if not isinstance(table, (tuple, list)) or len(table) != 3 or any(t is None for t in table):
+            raise _hip.FocusFlowHipError(f"{name}: table must be the tuple (pos, ids, age) of a track table, all three, or None")
+        pos, ids, age = table
+        if _track_table(name, pos, ids, age) != (b, n) or pos.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {dev}, got pos {tuple(pos.shape)} on {pos.device}")
+    return b, n, dev, pos, ids, age
+
+
 def _track_outs(name: str, out, specs, device):
     """out: None (new tensors) or one contiguous tensor per (what, shape, dtype) of `specs`, on `device`."""
     if out is None:
@@ -1255,23 +1276,9 @@ def fb_matches(matches: Tensor, valid: Tensor, bw: Tensor, left: int, top: int, 
     row, +inf where the target left the frame; status (B,N) uint8: 0 no row, 1 consistent, 2 the target left the frame, 3
     inconsistent); out: that tuple to write into (default: new tensors).  Exact.  Enqueues only, so it can be captured."""
     name = "fb_matches"
-    _require_device(matches, name, "matches", (torch.float32,))
-    _require_device(valid, name, "valid", (torch.uint8,))
-    if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: matches must be contiguous (B,N,4), got {tuple(matches.shape)} strides {matches.stride()}")
-    b, n, _ = matches.shape
-    if tuple(valid.shape) != (b, n) or not valid.is_contiguous() or valid.device != matches.device:
-        raise _hip.FocusFlowHipError(f"{name}: valid must be contiguous {(b, n)} on {matches.device}, got {tuple(valid.shape)} strides {valid.stride()} "
-                                     f"on {valid.device}")
-    _, hp, wp = _fb_field(name, bw, "bw", b, matches.device)
-    pos = ids = age = None
-    if table is not None:
-        if not isinstance(table, (tuple, list)) or len(table) != 3 or any(t is None for t in table):
-            raise _hip.FocusFlowHipError(f"{name}: table must be the tuple (pos, ids, age) of a track table, all three, or None")
-        pos, ids, age = table
-        if _track_table(name, pos, ids, age) != (b, n) or pos.device != matches.device:
-            raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {matches.device}, got pos {tuple(pos.shape)} on {pos.device}")
-    err2, status = _track_outs(name, out, (("err2", (b, n), torch.float32), ("status", (b, n), torch.uint8)), matches.device)
+    b, n, dev, pos, ids, age = _match_rows(name, matches, valid, table)
+    _, hp, wp = _fb_field(name, bw, "bw", b, dev)
+    err2, status = _track_outs(name, out, (("err2", (b, n), torch.float32), ("status", (b, n), torch.uint8)), dev)
     _hip.call("ff_fb_matches", _p(matches), _p(valid), n, _p(bw), bw.stride(0), bw.stride(1), bw.stride(2), bw.stride(3), b, int(left), int(top), int(h),
               int(w), hp, wp, float(alpha), float(beta), _p(pos), _p(ids), _p(age), _p(err2), _p(status), _stream())
     return err2, status
@@ -1282,36 +1289,38 @@ def epipolar_ws(b: int, n: int, hypotheses: int) -> int:
     return _hip.load().ff_epipolar_ws(int(b), int(n), int(hypotheses))
 
 
-def _ransac_args(name: str, matches: Tensor, valid: Tensor, epoch: Tensor, table):
-    """What epipolar_ransac and homography_ransac ask of their common arguments.  -> (B, N, device, pos, ids, age)"""
-    _require_device(matches, name, "matches", (torch.float32,))
-    _require_device(valid, name, "valid", (torch.uint8,))
-    if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: matches must be contiguous (B,N,4), got {tuple(matches.shape)} strides {matches.stride()}")
-    b, n, _ = matches.shape
-    dev = matches.device
-    if tuple(valid.shape) != (b, n) or not valid.is_contiguous() or valid.device != dev:
-        raise _hip.FocusFlowHipError(f"{name}: valid must be contiguous {(b, n)} on {dev}, got {tuple(valid.shape)} strides {valid.stride()} on {valid.device}")
+def _ransac(check: str, model: str, matches: Tensor, valid: Tensor, h, w, threshold, hypotheses, min_inliers, permilles, seed, epoch: Tensor, table, cull,
+            out, ws: Optional[Tensor], hold: Optional[Tensor] = None):
+    """The body of epipolar_ransac and homography_ransac: ff_<check>_ransac on a matches / valid pair.  model: the name of the
+    (B,3,3) output; permilles: (permille,), or (permille, planar_permille) for a check with a `planar` output.  -> the outputs"""
+    name = f"{check}_ransac"
+    b, n, dev, pos, ids, age = _match_rows(name, matches, valid, table)
     _require_device(epoch, name, "epoch", (torch.int32,))
     if epoch.numel() != 1 or epoch.device != dev:
         raise _hip.FocusFlowHipError(f"{name}: epoch must be one int32 on {dev}, got {tuple(epoch.shape)} on {epoch.device}")
-    pos = ids = age = None
-    if table is not None:
-        if not isinstance(table, (tuple, list)) or len(table) != 3 or any(t is None for t in table):
-            raise _hip.FocusFlowHipError(f"{name}: table must be the tuple (pos, ids, age) of a track table, all three, or None")
-        pos, ids, age = table
-        if _track_table(name, pos, ids, age) != (b, n) or pos.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {dev}, got pos {tuple(pos.shape)} on {pos.device}")
-    return b, n, dev, pos, ids, age
-
-
-def _ransac_ws(name: str, ws: Optional[Tensor], nbytes: int, dev) -> Tensor:
+    if check == "homography" and matches.data_ptr() % 16:
+        raise _hip.FocusFlowHipError(f"{name}: matches must be 16-byte aligned (a view that starts inside a row is not)")
+    per_sample = [("inliers", torch.int32), ("candidates", torch.int32), ("ok", torch.uint8)] + [("planar", torch.uint8)] * (len(permilles) == 2)
+    res = _track_outs(name, out, ((model, (b, 3, 3), torch.float32), *((what, (b,), dtype) for what, dtype in per_sample),
+                                  ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
+    nbytes = getattr(_hip.load(), f"ff_{check}_ws")(b, n, int(hypotheses))
     if ws is None:
-        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # (an unsupported shape is refused by the call itself, with its reason)
-    _require_device(ws, name, "ws", (torch.uint8,))
-    if ws.numel() < nbytes or not ws.is_contiguous() or ws.device != dev:
-        raise _hip.FocusFlowHipError(f"{name}: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, got {ws.numel()} on {ws.device}")
-    return ws
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # (an unsupported shape is refused by the call itself, with its reason)
+    else:
+        _require_device(ws, name, "ws", (torch.uint8,))
+        if ws.numel() < nbytes or not ws.is_contiguous() or ws.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, got {ws.numel()} on {ws.device}")
+    entry, tail = f"ff_{check}_ransac", ()
+    if hold is not None:
+        _require_device(hold, name, "hold", (torch.uint8,))
+        if tuple(hold.shape) != (b,) or not hold.is_contiguous() or hold.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: hold must be contiguous {(b,)} on {dev}, got {tuple(hold.shape)} on {hold.device}")
+        entry, tail = entry + "_hold", (_p(hold),)
+    m3, *per_sample, status, dist2 = res      # (the C entries take dist2 and status before the per-sample outputs)
+    _hip.call(entry, _p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), *map(int, permilles),
+              int(seed) & 0xffffffff, _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(m3), _p(dist2), _p(status), *map(_p, per_sample), _p(ws),
+              ws.numel(), *tail, _stream())
+    return res
 
 
 def epipolar_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: float, hypotheses: int, min_inliers: int, permille: int, seed: int,
@@ -1329,22 +1338,7 @@ def epipolar_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold: f
     bytes to work in (default: a new one per call).  hold: None, or (B) uint8 on the device (ff_epipolar_ransac_hold): a sample
     whose byte is not 0 gets no verdict - ok 0, F zero, valid and the table left alone -, as homography_ransac's `planar` asks
     where F is under-determined.  Exact.  Enqueues only, so it can be captured."""
-    name = "epipolar_ransac"
-    b, n, dev, pos, ids, age = _ransac_args(name, matches, valid, epoch, table)
-    F, inliers, candidates, ok, status, dist2 = _track_outs(name, out, (("F", (b, 3, 3), torch.float32), ("inliers", (b,), torch.int32),
-                                                                        ("candidates", (b,), torch.int32), ("ok", (b,), torch.uint8),
-                                                                        ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
-    ws = _ransac_ws(name, ws, epipolar_ws(b, n, hypotheses), dev)
-    args = (_p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), int(permille), int(seed) & 0xffffffff,
-            _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(F), _p(dist2), _p(status), _p(inliers), _p(candidates), _p(ok), _p(ws), ws.numel())
-    if hold is None:
-        _hip.call("ff_epipolar_ransac", *args, _stream())
-    else:
-        _require_device(hold, name, "hold", (torch.uint8,))
-        if tuple(hold.shape) != (b,) or not hold.is_contiguous() or hold.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: hold must be contiguous {(b,)} on {dev}, got {tuple(hold.shape)} on {hold.device}")
-        _hip.call("ff_epipolar_ransac_hold", *args, _p(hold), _stream())
-    return F, inliers, candidates, ok, status, dist2
+    return _ransac("epipolar", "F", matches, valid, h, w, threshold, hypotheses, min_inliers, (permille,), seed, epoch, table, cull, out, ws, hold)
 
 
 def homography_ws(b: int, n: int, hypotheses: int) -> int:
@@ -1364,18 +1358,7 @@ def homography_ransac(matches: Tensor, valid: Tensor, h: int, w: int, threshold:
     int32; ok (B) uint8; planar (B) uint8; status (B,N) uint8 as epipolar_ransac; dist2 (B,N) fp32 px^2: -1 no row, +inf without a
     verdict and where the map sends the point behind the plane at infinity); out: that tuple to write into.  ws: a uint8 device
     tensor of homography_ws(B, N, hypotheses) bytes.  Exact.  Enqueues only, so it can be captured."""
-    name = "homography_ransac"
-    b, n, dev, pos, ids, age = _ransac_args(name, matches, valid, epoch, table)
-    if matches.data_ptr() % 16:
-        raise _hip.FocusFlowHipError(f"{name}: matches must be 16-byte aligned (a view that starts inside a row is not)")
-    H, inliers, candidates, ok, planar, status, dist2 = _track_outs(
-        name, out, (("H", (b, 3, 3), torch.float32), ("inliers", (b,), torch.int32), ("candidates", (b,), torch.int32), ("ok", (b,), torch.uint8),
-                    ("planar", (b,), torch.uint8), ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
-    ws = _ransac_ws(name, ws, homography_ws(b, n, hypotheses), dev)
-    _hip.call("ff_homography_ransac", _p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), int(permille),
-              int(planar_permille), int(seed) & 0xffffffff, _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(H), _p(dist2), _p(status),
-              _p(inliers), _p(candidates), _p(ok), _p(planar), _p(ws), ws.numel(), _stream())
-    return H, inliers, candidates, ok, planar, status, dist2
+    return _ransac("homography", "H", matches, valid, h, w, threshold, hypotheses, min_inliers, (permille, planar_permille), seed, epoch, table, cull, out, ws)
 
 
 def homography_residual(flow: Tensor, H: Tensor, ok: Tensor, out: Optional[Tensor] = None) -> Tensor:

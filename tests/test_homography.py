@@ -367,7 +367,7 @@ def test_homography_kernels_do_not_spill():
     assert len(kernels) >= 5, kernels      # compact, hypotheses, score, select, residual
     spilled = {k["name"]: int(k.get("ScratchSize", "0")) for k in kernels if int(k.get("ScratchSize", "0")) > 0}
     assert not spilled, f"homography.hip: kernels with scratch (bytes per lane): {spilled}"
-    hyp = [k for k in kernels if "hom_hypotheses_kernel" in k["name"]]
+    hyp = [k for k in kernels if "ransac_hypotheses_kernel" in k["name"] and "Homography" in k["name"]]      # (the template's instantiation)
     assert len(hyp) == 1 and 64 * 72 * 4 <= int(hyp[0].get("LDS", "0")) <= 65536, f"the hypotheses kernel keeps 64 systems of 8 x 9 in LDS: {hyp}"
     res = [k for k in kernels if "hom_residual_kernel" in k["name"]]
     assert len(res) == 1 and int(res[0].get("LDS", "0")) == 0, res
