@@ -7,7 +7,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float act_grad_from_output(float y, int act) {
     switch (act) {

@@ -17,7 +17,7 @@
 // Matrix form: v_mfma_f32_16x16x32_f16, A = weights (rows = 16 output channels), B = 16 pixels of one patch row; a lane
 // then owns FOUR CONSECUTIVE CHANNELS of a pixel (the epilogue's 16-byte loads / stores, and the two 8-byte stores of a
 // split-pair output).  Arithmetic and summation order are those of conv_patch.hip's 16x16x32 variant: chunk -> tap ->
-// three terms (w0 x0, w1 x0, w0 x1), so a layer computes the same bits whichever of the two kernels runs it.
+// three terms (ff::mfma16_terms, split_mfma.h: w0 x0, w1 x0, w0 x1), so a layer computes the same bits whichever of the two kernels runs it.
 //
 // LDS image of a patch: row r = py * PW + px (PW = 16 + KW - 1, even), 128 bytes per row, the eight 16-byte slots of a
 // row XOR-swizzled by (px >> 1) & 7 ON THE SOURCE SIDE (a DMA lane picks which slot of its pixel it fetches).  A B-fragment
@@ -33,15 +33,11 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char* lds_ptr_t;
-
-__device__ __forceinline__ int PI16(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9); }
+using ff::OOB;
 
 struct DArgs {
     FFConvParams p;
@@ -50,30 +46,12 @@ struct DArgs {
     long long w_row_bytes;
 };
 
-__device__ __forceinline__ f16x8 lds_ld16(unsigned addr) { return *(__attribute__((address_space(3))) const f16x8*)(unsigned long)addr; }
-
 #if defined(FF_LAB) && !defined(FF_DMA_STAMPS)
 #define FF_DMA_STAMPS 1       // the lab build stamps its blocks' phases (tools/dma_stamps.py); FF_DMA_ABL=<bits> adds timing-only ablations
 #endif
 #ifndef FF_DMA_NSET
 #define FF_DMA_NSET 2      // weight register sets of the three-waves-per-SIMD instances.  3 (two taps of lead) was measured with in-kernel
 #endif                     // stamps on the 3x3 layers: main loop 44.4 vs 42.2 us (256->192), 24.5 vs 23.4 us (128->512) - slower; kept as a lab switch
-constexpr unsigned OOB = 0x7fffffffu;     // + any soffset < 2^31 stays below 2^32: the range check sees it out of range -> zeros
-
-// one LDS-DMA piece: 64 lanes x 16 bytes -> 1 KB at LDS address `dst` (M0), source = rsrc base + voff + soff
-__device__ __forceinline__ void dma_piece(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned dst, unsigned soff) {
-    unsigned keep;
-    // (uniform values: when the scalar registers run short the allocator parks them in a vector register, which these operands do not take)
-    dst = (unsigned)__builtin_amdgcn_readfirstlane((int)dst);
-    soff = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(rs), "s"(dst), "s"(soff)
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // KH x KW taps; TH pixel rows x 16 columns per block; NV 16-channel tiles per wave (block = 4 waves = 64 NV channels)
 // EPI: FFConvParams.ep_mode (GRU steps, motion tail); TERMS 3 (f16x3) or 1 (f16)
@@ -151,7 +129,7 @@ __device__ __forceinline__ void conv_dma_body(const DArgs& a) {
         for (int j = 0; j < NPP; ++j) {
             if ((wave + NW * j) < NPIECE) {       // wave-uniform
                 const unsigned voff = ppix[j] >= 0 ? __umul24((unsigned)(ppix[j] >> 7), (unsigned)ldb) + (unsigned)(ppix[j] & 127) : OOB;
-                dma_piece(voff, rs, lds0 + buf * PBYTES + (wave + NW * j) * 1024, soff);
+                ff::dma_piece<true>(voff, rs, lds0 + buf * PBYTES + (wave + NW * j) * 1024, soff);
             }
         }
     };
@@ -204,7 +182,7 @@ __device__ __forceinline__ void conv_dma_body(const DArgs& a) {
                 }
                 if (!(cv_key[i] & 8u)) v0 = v1 = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
-            ff::ff_f16x4 h00, h01, h10, h11;
+            f16x4 h00, h01, h10, h11;
             ff::split_pair4(v0 * xs, h00, h10);
             ff::split_pair4(v1 * xs, h01, h11);
             f16x8 x0, x1;
@@ -244,14 +222,11 @@ __device__ __forceinline__ void conv_dma_body(const DArgs& a) {
         constexpr int SET = decltype(set_tag)::value;
         const int soff = kc * kc_stride;
 #pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            wr[SET][v][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, woff[v], soff, 0));
-            if (TERMS == 3) wr[SET][v][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, woff[v] + term_off, soff, 0));
-        }
+        for (int v = 0; v < NV; ++v) ff::load_w_frag<TERMS>(rsw, woff[v], soff, wr[SET][v], term_off);
     };
 
     // ---- B fragments: pixel column PI16(i) + dx of patch row u + dy
-    const int pcol = PI16(i16);
+    const int pcol = ff::PI16(i16);
 
     f32x4 acc[NV][TH];
 #pragma unroll
@@ -286,7 +261,7 @@ __device__ __forceinline__ void conv_dma_body(const DArgs& a) {
 #else
         if (t == 0) {
 #endif
-            wait_vm<NWL>();
+            ff::wait_vm<NWL>();
             __builtin_amdgcn_s_barrier();      // every wave's pieces of patch c have landed; everybody is done with the other buffer
             if constexpr (XF32) {              // fp32 patch -> split pairs, in place; nobody reads a fragment before everybody has converted
                 convert(c, c & 1);
@@ -315,19 +290,10 @@ __device__ __forceinline__ void conv_dma_body(const DArgs& a) {
             constexpr int LO = decltype(lo_tag)::value, HI = decltype(hi_tag)::value;
 #pragma unroll
             for (int u = LO; u < HI; ++u) {
-                const f16x8 xa = lds_ld16(xa0 + u * PW * 128);
-                f16x8 xb;
-                if (TERMS == 3) xb = lds_ld16(xa1 + u * PW * 128);
+                const f16x8 xa = ff::lds_ld16(xa0 + u * PW * 128);
+                const f16x8 xb = TERMS == 3 ? ff::lds_ld16(xa1 + u * PW * 128) : xa;
 #pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    const f16x8 w0 = __builtin_bit_cast(f16x8, wr[CUR][v][0]);
-                    acc[v][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xa, acc[v][u], 0, 0, 0);
-                    if (TERMS == 3) {
-                        const f16x8 w1 = __builtin_bit_cast(f16x8, wr[CUR][v][1]);
-                        acc[v][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, xa, acc[v][u], 0, 0, 0);
-                        acc[v][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xb, acc[v][u], 0, 0, 0);
-                    }
-                }
+                for (int v = 0; v < NV; ++v) ff::mfma16_terms<TERMS>(acc[v][u], wr[CUR][v][0], wr[CUR][v][1], xa, xb);
             }
             // schedule: the fragment reads run two pixel rows ahead of the MFMAs (three rows of fragments live, not all)
             constexpr int RD = TERMS == 3 ? 2 : 1, N = HI - LO, LEAD = N < 2 ? N : 2;

@@ -23,12 +23,10 @@
 // The fp32 MFMA is an exact k-ordered fmaf chain (no reduced precision), which
 // is what lets the path hold the reference's fp32 results to ~1e-6.
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32;
 
@@ -40,7 +38,7 @@ struct KernArgs {
     int m_tiles, n_tiles;
 };
 
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
+using ff::swz;
 
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(256) void conv_fwd_kernel(const KernArgs a) {

@@ -17,14 +17,12 @@
 // hipcc-flags: -ffp-contract=off
 #include <algorithm>
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using ff::PI16;
+using ff::KG16;
 
 constexpr int TW = 16, ROWB = 128;   // tile height TH = 4*TM (template): 16, 8 or 4 rows; BN = 64*TN output channels
 // LDS rows (one patch pixel / one weight row: 32 x0 + 32 x1 halfs = 128 B) sit at a 144-byte pitch instead of being
@@ -33,10 +31,6 @@ constexpr int TW = 16, ROWB = 128;   // tile height TH = 4*TM (template): 16, 8 
 // immediate offset from one base register.  PMC on the swizzled version: 35 % of the LDS-active cycles were
 // bank-conflict cycles and the kernel issued 10 VALU instructions per MFMA, mostly swizzle arithmetic.
 constexpr int ROWP = 144;
-// MF16: row i of a 16-row MFMA tile <-> position in the tile (pixel column / LDS row of the weight tile)
-__device__ __forceinline__ int PI16(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9); }
-__device__ __forceinline__ int KG16(int g) { return ((g & 1) << 1) | (g >> 1); }     // place of k-group g inside a term's 64 bytes
-
 
 struct PArgs {
     FFConvParams p;
@@ -45,15 +39,6 @@ struct PArgs {
     long long w_row_bytes;
     int nci_split;           // SPLITK: input chunks per K split (blockIdx.y), partial sums to p.splitk_ws
 };
-
-__device__ __forceinline__ void split4(const f32x4 v, f16x4& h0, f16x4& h1) {     // both halves on v's scale (ff_common.h)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const _Float16 a = (_Float16)v[j];
-        h0[j] = a;
-        h1[j] = (_Float16)(v[j] - (float)a);
-    }
-}
 
 // NITEM = patch items per thread; TM x TN = 32-pixel x 32-channel MFMA tiles per wave (block: 2 x 2 waves =
 // 64 TM pixels x 64 TN channels); ABL = timing-only ablation
@@ -123,7 +108,7 @@ __device__ __forceinline__ void conv_patch_body(const PArgs& a) {
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
         const int n = n0 + (tid >> 3) + 32 * i;
-        woff[i] = n < p.Cout ? (int)(n * a.w_row_bytes) + kq * 16 : 0x7fffffff;
+        woff[i] = n < p.Cout ? (int)(n * a.w_row_bytes) + kq * 16 : (int)ff::OOB;
     }
 
     f32x4 rp[NITEM], rw[NW];
@@ -143,7 +128,7 @@ __device__ __forceinline__ void conv_patch_body(const PArgs& a) {
         const int cib = (ci0 + kq * 4) * 4;
 #pragma unroll
         for (int i = 0; i < NITEM; ++i) {
-            const int off = ppix[i] >= 0 ? ppix[i] * ldb + cib : 0x7fffffff;     // out of range -> zeros
+            const int off = ppix[i] >= 0 ? ppix[i] * ldb + cib : (int)ff::OOB;     // out of range -> zeros
             rp[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
         }
     };
@@ -163,7 +148,7 @@ __device__ __forceinline__ void conv_patch_body(const PArgs& a) {
                     }
                     if (ppix[i] < 0) v = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
-                split4(v * xs, h0, h1);
+                ff::split4(v * xs, h0, h1);
                 *reinterpret_cast<f16x4*>(sP + row * ROWP + pc * 16 + half) = h0;
                 if (TERMS == 3) *reinterpret_cast<f16x4*>(sP + row * ROWP + 64 + pc * 16 + half) = h1;
             }
@@ -223,16 +208,9 @@ __device__ __forceinline__ void conv_patch_body(const PArgs& a) {
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
                     const f16x8 xa = *reinterpret_cast<const f16x8*>(pa + u * PW * ROWP);
-                    f16x8 xb;
-                    if (TERMS == 3) xb = *reinterpret_cast<const f16x8*>(pa + u * PW * ROWP + 64);
+                    const f16x8 xb = TERMS == 3 ? *reinterpret_cast<const f16x8*>(pa + u * PW * ROWP + 64) : xa;
 #pragma unroll
-                    for (int v = 0; v < NV; ++v) {
-                        acc[v][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[v], xa, acc[v][u], 0, 0, 0);
-                        if (TERMS == 3) {
-                            acc[v][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[v], xa, acc[v][u], 0, 0, 0);
-                            acc[v][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[v], xb, acc[v][u], 0, 0, 0);
-                        }
-                    }
+                    for (int v = 0; v < NV; ++v) ff::mfma16_terms<TERMS>(acc[v][u], w0[v], w1[v], xa, xb);
                 }
                 if (!last) {                  // next tap's weights go to the other buffer
                     if (WB == 1) __syncthreads();     // ... or, with one buffer, wait until everybody has read this tap's
@@ -423,6 +401,8 @@ __device__ __forceinline__ void conv_patch_body(const PArgs& a) {
                             if (TERMS == 3) asm volatile("" :: "v"(a1[t]), "v"(b1[j]));
                             continue;
                         }
+                        // ff::mfma32_terms<TERMS, true>'s order, written out: through the helper the one-tile instances (TM = TN = 1)
+                        // come out of the optimiser with a differently threaded epilogue - other machine code
                         acc[t][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[t], b0[j], acc[t][j], 0, 0, 0);
                         if (TERMS == 3) {
                             acc[t][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[t], b1[j], acc[t][j], 0, 0, 0);

@@ -16,7 +16,7 @@
 //     its weights straight into registers in fragment order (ff_pack_frag16, as conv_dma.hip's main loop): no weights in LDS,
 //     the next tap's loads in flight behind the current tap's MFMAs;
 //   * ten tap steps per chunk: nine into A's accumulators, the centre tap's rows again with the shortcut's weights into D's;
-//     v_mfma_f32_16x16x32_f16 with A = weights, B = 16 pixels, terms in conv_dma.hip's order (w0 x0, w1 x0, w0 x1);
+//     v_mfma_f32_16x16x32_f16 with A = weights, B = 16 pixels, terms in ff::mfma16_terms' order (split_mfma.h: w0 x0, w1 x0, w0 x1);
 //   * a lane's accumulator holds four consecutive channels of one pixel: the epilogue - acc / 64 + bias, optional per-channel
 //     scale and shift (folded eval BatchNorm), activation, as separately rounded operations - leaves as 16-byte buffer stores;
 //   * statistics (optional per output): every lane reduces what it stores to {pivot, sum(v - pivot), sum((v - pivot)^2), n} per
@@ -24,16 +24,9 @@
 //     [B][tiles][Cout][4] for ff_norm_stats_finish.
 // hipcc-flags: -ffp-contract=off
 #include <algorithm>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-
-__device__ __forceinline__ int PI16(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9); }
-__device__ __forceinline__ int slot_of(int g) { return ((g & 1) << 1) | (g >> 1); }      // k-groups in the order 0, 2, 1, 3
 
 constexpr int TH = 4, TW = 16;                  // output tile
 constexpr int PH = 2 * TH + 1, PW = 2 * TW + 1; // input patch: 9 x 33
@@ -73,7 +66,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 8
         const bool ok = i < NITEM && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
         goff[j] = ok ? ((unsigned)((b * H + iy) * W + ix) * (unsigned)p.x_ld) * 4u + q * 16 : OOB;
         const int idx = (c & 1) ? NEV + (c >> 1) : (c >> 1);
-        loff[j] = (r * PW + idx) * PITCH + slot_of(q >> 1) * 16 + (q & 1) * 8;
+        loff[j] = (r * PW + idx) * PITCH + ff::KG16(q >> 1) * 16 + (q & 1) * 8;
     }
 
     // ---- this wave's weights: [Cout / 16][K chunks][term][lane][16 B]; the 3x3 rows are [tap][Cin]
@@ -84,14 +77,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 8
     f32x4 acc_a[TH], acc_d[TH];
 #pragma unroll
     for (int py = 0; py < TH; ++py) acc_a[py] = acc_d[py] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int pxl = PI16(i16);
-    const char* bp = smem + pxl * PITCH + slot_of(g16) * 16;
+    const int pxl = ff::PI16(i16);
+    const char* bp = smem + pxl * PITCH + ff::KG16(g16) * 16;
 
-    auto load_w = [&](const __amdgpu_buffer_rsrc_t r, int off, f32x4 (&wv)[2]) {
-        wv[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-        if (TERMS == 3) wv[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off + 1024, 0, 0));
-    };
+    auto load_w = [&](const __amdgpu_buffer_rsrc_t r, int off, f32x4 (&wv)[2]) { ff::load_w_frag<TERMS>(r, off, 0, wv); };
     auto tap_step = [&](const char* xp, const f32x4 (&wv)[2], f32x4 (&acc)[TH]) {      // one tap of one chunk over the tile's four rows
+        // (ff::mfma16_terms' order written out: this kernel reads the x1 fragment BETWEEN the first term and the other two, which
+        // the shared step - all operands before the first MFMA - schedules differently)
         const f16x8 w0 = __builtin_bit_cast(f16x8, wv[0]);
         f16x8 w1;
         if (TERMS == 3) w1 = __builtin_bit_cast(f16x8, wv[1]);
@@ -123,10 +115,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 8
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 if (j == NJ - 1 && tid + j * NT >= NITEM) continue;
-                ff::ff_f16x4 h0, h1;
+                f16x4 h0, h1;
                 ff::split_pair4(val[j], h0, h1);
-                *reinterpret_cast<ff::ff_f16x4*>(smem + loff[j]) = h0;
-                if (TERMS == 3) *reinterpret_cast<ff::ff_f16x4*>(smem + loff[j] + 64) = h1;
+                *reinterpret_cast<f16x4*>(smem + loff[j]) = h0;
+                if (TERMS == 3) *reinterpret_cast<f16x4*>(smem + loff[j] + 64) = h1;
             }
         }
         __syncthreads();

@@ -10,7 +10,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int RUN = 8;
 
 struct SArgs {

@@ -17,14 +17,11 @@
 // in registers on their way to LDS.  Operands must satisfy |x| < 65504.
 #include <algorithm>
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using ff::swz;
 
 constexpr int BK = 32;
 constexpr int ROWB = 128;   // bytes per LDS row = per 32-k chunk of one packed weight row
@@ -35,17 +32,6 @@ struct KernArgs {
     int m_tiles, n_tiles;
     long long w_row_bytes;   // packed split weights: bytes per output channel
 };
-
-__device__ __forceinline__ int swz(int row, int piece) { return piece ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void split4(const f32x4 v, f16x4& h0, f16x4& h1) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const _Float16 a = (_Float16)v[j];
-        h0[j] = a;
-        h1[j] = (_Float16)(v[j] - (float)a);
-    }
-}
 
 template <int WM, int WN, int TM, int TN, int TERMS, int NST, bool UNI, int NB>   // NB = LDS buffers per operand (2, or 1: see _occ)
 __device__ __forceinline__ void conv_split_body(const KernArgs& a) {
@@ -127,7 +113,7 @@ __device__ __forceinline__ void conv_split_body(const KernArgs& a) {
 #pragma unroll
     for (int i = 0; i < LB; ++i) {
         const int n = n0 + rbase + 32 * i;
-        woff[i] = n < p.Cout ? (int)(n * a.w_row_bytes) + kq * 16 : 0x7fffffff;   // out of range -> zeros
+        woff[i] = n < p.Cout ? (int)(n * a.w_row_bytes) + kq * 16 : (int)ff::OOB;   // out of range -> zeros
     }
     auto stage_load_uni = [&](int kc, f32x4 (&ra)[LA], f32x4 (&rb)[LB]) {
         // block-uniform decode of chunk kc (scalar unit): K order is (tap, ci)
@@ -146,7 +132,7 @@ __device__ __forceinline__ void conv_split_body(const KernArgs& a) {
 #pragma unroll
         for (int i = 0; i < LA; ++i) {
             const bool ok = (vmask[i] >> tap) & 1ull;
-            const int off = ok ? (pixoff[i] + dpix) * ldb + cib : 0x7fffffff;
+            const int off = ok ? (pixoff[i] + dpix) * ldb + cib : (int)ff::OOB;
             ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
         }
 #pragma unroll
@@ -191,7 +177,7 @@ __device__ __forceinline__ void conv_split_body(const KernArgs& a) {
         for (int i = 0; i < LA; ++i) {
             const int row = rbase + 32 * i;
             f16x4 h0, h1;
-            split4(ra[i] * xs, h0, h1);
+            ff::split4(ra[i] * xs, h0, h1);
             *reinterpret_cast<f16x4*>(dA + row * ROWB + swz(row, pc) * 16 + half) = h0;
             if (TERMS == 3) *reinterpret_cast<f16x4*>(dA + row * ROWB + swz(row, 4 + pc) * 16 + half) = h1;
         }
@@ -233,13 +219,8 @@ __device__ __forceinline__ void conv_split_body(const KernArgs& a) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[i], b0[j], acc[i][j], 0, 0, 0);
-                    if (TERMS == 3) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[i], b1[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[i], b0[j], acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < TN; ++j)
+                    ff::mfma32_terms<TERMS, true>(acc[i][j], a0[i], a1[i], b0[j], b1[j]);
         }
     };
     // Register ring: chunk c lives in stage c % NST from its load until it is written to LDS.

@@ -16,14 +16,9 @@
 //     activation, and the InstanceNorm statistics of the output (FFConvParams.stats_part).
 #include <algorithm>
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 16;                 // output tile
 constexpr int PR = 2 * TH + 5, PC = 2 * TW + 6;  // patch: 21 rows x 38 columns (column 37 only meets the zero tap kx' = 7)
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const SArgs a) {
     const int wm = wave & 1, wn = wave >> 1;
     const int li = lane & 31, lh = lane >> 5;
     const int H = p.H, W = p.W, Ho = p.Ho, Wo = p.Wo;
-    const float xs = ff::XSPLIT, xinv = ff::SPLIT_INV;
+    const float xinv = ff::SPLIT_INV;
 
     // ---- weights of this wave's 32 channels, all 14 steps x two halves, in registers.  Step s = (ky, h): taps
     // kx = 4h + 2lh and 4h + 2lh + 1 (the latter zero when it is 7) x 4 channels; packed row: k = (ky*7 + kx)*4 + c.
@@ -105,13 +100,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const SArgs a) {
         for (int i = 0; i < NSLOT; ++i) {
             if (slot_off[i] < 0) continue;
             f16x4 h0, h1;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float sv = stage[i][j] * xs;
-                const _Float16 t = (_Float16)sv;
-                h0[j] = t;
-                h1[j] = (_Float16)(sv - (float)t);
-            }
+            ff::split_pair4(stage[i], h0, h1);
             *reinterpret_cast<f16x4*>(base + slot_off[i]) = h0;
             *reinterpret_cast<f16x4*>(base + PLANE + slot_off[i]) = h1;
         }
@@ -145,9 +134,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const SArgs a) {
             for (int t = 0; t < 2; ++t) {
                 const f16x8 x0 = *reinterpret_cast<const f16x8*>(pb + aoff[t] + so);
                 const f16x8 x1 = *reinterpret_cast<const f16x8*>(pb + PLANE + aoff[t] + so);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, w0[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, w1[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, w0[s], acc[t], 0, 0, 0);
+                ff::mfma32_terms<3, true>(acc[t], x0, x1, w0[s], w1[s]);
             }
         }
 

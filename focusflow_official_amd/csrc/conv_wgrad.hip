@@ -15,12 +15,10 @@
 // 128x64) tile into dW with fp32 atomics (128-byte row segments per wave
 // instruction = full atomic rate).  dW must be zeroed by the caller.
 // With groups = B and a 1x1 kernel this is also d(corr volume)/d(fmap2).
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RK = 32;   // pixels per reduction chunk
 

@@ -18,14 +18,10 @@
 // Block = 4 waves = 2 (32-channel halves of co) x 2 (tap groups); a k-slice is one 16-pixel tile row.
 #include <algorithm>
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short v4s __attribute__((__vector_size__(4 * sizeof(short))));
 
 constexpr int TW = 16, TH = 8, NPIX = TW * TH;
@@ -40,15 +36,6 @@ struct WpArgs {
     int K, Cin, nci;  // K = KH*KW*Cin, nci = Cin / 32
     int tiles_x, tiles_y, tiles, tiles_per_block;
 };
-
-__device__ __forceinline__ void split4(const f32x4 v, f16x4& h0, f16x4& h1) {     // both halves on v's scale (ff_common.h)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const _Float16 a = (_Float16)v[j];
-        h0[j] = a;
-        h1[j] = (_Float16)(v[j] - (float)a);
-    }
-}
 
 __device__ __forceinline__ f16x4 tr_read(const char* p) {
     const v4s r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(p));
@@ -100,20 +87,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const long long pixels = (long long)p.B * H * W;
     const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.y), 0, (int)(pixels * p.y_ld * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xseg), 0, (int)(pixels * xld * 4), 0x00020000);
-    const int ycol = yok ? (co0 + yq * 4) * 4 : 0x7fffffff, xcol = (xc + xq * 4) * 4;
+    const int ycol = yok ? (co0 + yq * 4) * 4 : (int)ff::OOB, xcol = (xc + xq * 4) * 4;
     auto load_tile = [&](int t) {
         const int b = t / (a.tiles_y * a.tiles_x), r = t - b * a.tiles_y * a.tiles_x;
         const int ty = r / a.tiles_x, y0 = ty * TH, x0 = (r - ty * a.tiles_x) * TW;
 #pragma unroll
         for (int i = 0; i < NYI; ++i) {
             const int px = ypx + 16 * i, y = y0 + (px >> 4), x = x0 + (px & 15);
-            const int off = (yok && y < H && x < W) ? ((b * H + y) * W + x) * (p.y_ld * 4) + ycol : 0x7fffffff;
+            const int off = (yok && y < H && x < W) ? ((b * H + y) * W + x) * (p.y_ld * 4) + ycol : (int)ff::OOB;
             ry[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsy, off, 0, 0));
         }
 #pragma unroll
         for (int i = 0; i < NXI; ++i) {
             const int px = xpx + 32 * i, py = px / PW, y = y0 - p.pad_h + py, x = x0 - p.pad_w + (px - py * PW);
-            const int off = (px < PPIX && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? ((b * H + y) * W + x) * (xld * 4) + xcol : 0x7fffffff;
+            const int off = (px < PPIX && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? ((b * H + y) * W + x) * (xld * 4) + xcol : (int)ff::OOB;
             rx[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, off, 0, 0));
         }
     };
@@ -124,7 +111,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             f16x4 h0, h1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) bsum[j] += ry[i][j];
-            split4(ry[i] * xs, h0, h1);
+            ff::split4(ry[i] * xs, h0, h1);
             char* d = sY + (ypx + 16 * i) * PY + yq * 8;
             *reinterpret_cast<f16x4*>(d) = h0;
             *reinterpret_cast<f16x4*>(d + 128) = h1;
@@ -134,7 +121,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int px = xpx + 32 * i;
             if (px < PPIX) {
                 f16x4 h0, h1;
-                split4(rx[i] * ff::XSPLIT, h0, h1);
+                ff::split4(rx[i] * ff::XSPLIT, h0, h1);
                 char* d = sX + px * PX + xq * 8;
                 *reinterpret_cast<f16x4*>(d) = h0;
                 *reinterpret_cast<f16x4*>(d + 64) = h1;
@@ -180,9 +167,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const char* px = aX + (y * PW * PX + tapoff[k]);
                 const f16x8 b0 = cat8(tr_read(px), tr_read(px + 4 * PX));
                 const f16x8 b1 = cat8(tr_read(px + 64), tr_read(px + 4 * PX + 64));
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[k], 0, 0, 0);
+                ff::mfma32_terms<3, true>(acc[k], a0, a1, b0, b1);      // dY0 x0, dY0 x1, dY1 x0
             }
         }
     }

@@ -22,14 +22,10 @@
 // and L2 traffic per MFMA.
 #include <algorithm>
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int RK = 32;            // pixels per chunk
@@ -187,13 +183,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_kernel(const WsArgs a) {
 #pragma unroll
             for (int i = 0; i < TA; ++i)
 #pragma unroll
-                for (int j = 0; j < TB; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(y0[i], x0[j], acc[i][j], 0, 0, 0);
-                    if (TERMS == 3) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(y0[i], x1[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(y1[i], x0[j], acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < TB; ++j) ff::mfma32_terms<TERMS, true>(acc[i][j], y0[i], y1[i], x0[j], x1[j]);      // dY0 x0, dY0 x1, dY1 x0
         }
         if (c + 1 < nch) stage_store(cur ^ 1);
         __syncthreads();

@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 #include <cstdlib>
 #include "ff_common.h"
+#include "corr_layout.h"
 
 namespace {
 
@@ -64,17 +65,7 @@ struct LookupArgs {
     int out_ld, radius, num_levels;
 };
 
-// One separately-rounded replay of the sampler's coordinate chain.
-__device__ __forceinline__ void tap_1d(float c, float inv_scale, int off, int n, int& i0, float& w1) {
-    const float cl = __fmul_rn(c, inv_scale);                 // coords / 2**i   (exact: power of two)
-    const float x = __fadd_rn(cl, (float)off);                // + delta
-    const float nm1 = (float)(n - 1);
-    const float g = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, x), nm1), 1.f);   // 2*x/(n-1) - 1
-    const float u = __fmul_rn(__fmul_rn(__fadd_rn(g, 1.f), 0.5f), nm1);  // ((g+1)/2)*(n-1)
-    const float f = floorf(u);
-    i0 = (int)f;
-    w1 = __fsub_rn(u, f);
-}
+using ff::tap_1d;
 
 __global__ __launch_bounds__(256) void lookup_kernel(const LookupArgs a) {
     const int win = 2 * a.radius + 1, per_lvl = win * win, nk = a.num_levels * per_lvl;

@@ -20,15 +20,11 @@
 // contiguous runs of NHWC rows), the B operand (the tile's 32 fmap1 rows) is staged once per tile in LDS.
 #pragma clang fp contract(off)
 #include <cstdint>
-#include "ff_common.h"
+#include "split_mfma.h"
 #include "corr_alt_taps.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CH = 256;               // feature channels
 constexpr int ROWB = 1024;            // bytes of one operand row
@@ -83,9 +79,7 @@ __device__ __forceinline__ void d_block(const AltArgs& a, char* sm, int lv, long
                 const f16x8 a1 = *reinterpret_cast<const f16x8*>(arow + off + 64);
                 const f16x8 b0 = *reinterpret_cast<const f16x8*>(brow + off);
                 const f16x8 b1 = *reinterpret_cast<const f16x8*>(brow + off + 64);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc, 0, 0, 0);
+                ff::mfma32_terms<3, true>(acc, a0, a1, b0, b1);      // a0 b0, a0 b1, a1 b0 (corr_build.hip's order)
             }
     } else {
         // exact fp32: the half-wave hh sums channels 128 hh .. 128 hh + 127, one channel per MFMA step (the order of k is free)

@@ -22,13 +22,11 @@
 // third split operand per pass; DESIGN.md §4 gives what the exact form costs.
 #pragma clang fp contract(off)
 #include <cstdint>
-#include "ff_common.h"
+#include "split_mfma.h"
 #include "corr_alt_taps.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CH = 256;               // feature channels
 constexpr int TQX = 8, TQY = 4, TQ = TQX * TQY;

@@ -17,16 +17,12 @@
 // level 3 needs one exchange between the two half-waves.  Everything is transposed through LDS on the way out so that
 // every global store instruction writes whole 128-byte lines (16 bytes per lane).
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 #include "corr_layout.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct BuildArgs {
@@ -49,8 +45,6 @@ struct BuildArgs {
 constexpr int STAGE = 32768;     // J tile 16 KB | I tile 16 KB
 constexpr int NCHUNK = 8;        // C = 256 in chunks of 32 channels
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <bool HALF>
 __global__ __launch_bounds__(256, 2) void corr_build_kernel(const BuildArgs a) {
@@ -135,11 +129,7 @@ __global__ __launch_bounds__(256, 2) void corr_build_kernel(const BuildArgs a) {
                 j1[t] = *reinterpret_cast<const f16x8*>(jrow + bo + t * 4096 + so[1][s]);
             }
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(j0[t], i0, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(j0[t], i1, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(j1[t], i0, acc[t], 0, 0, 0);
-            }
+            for (int t = 0; t < 4; ++t) ff::mfma32_terms<3, true>(acc[t], j0[t], j1[t], i0, i1);      // j0 i0, j0 i1, j1 i0
         }
     }
     __syncthreads();      // operands are dead: each wave now owns 16 KB of LDS for its 32 queries
@@ -298,7 +288,6 @@ __global__ __launch_bounds__(256, 2) void corr_build_kernel(const BuildArgs a) {
             if (q < a.Q) {
                 char* dst = a.lvl[1] + (plane0 + q) * a.plane_bytes[1] +
                             (size_t)(((py >> 1) * a.ntx[1] + px) * 128 + (((4 * py) & 7) + piece) * 16);
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 u32x4 d = {wds[0], wds[1], wds[2], wds[3]};
                 *reinterpret_cast<u32x4*>(dst) = d;
             }

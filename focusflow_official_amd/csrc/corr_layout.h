@@ -9,8 +9,22 @@
 // (ff_corr_build clears what its patches do not cover; ff_corr_retile fills zero-initialised storage; the backward
 // kernels mask their updates), so the lookup needs no per-element masks.
 #pragma once
+#include <hip/hip_runtime.h>
 
 namespace ff {
+
+// One separately-rounded replay of the sampler's coordinate chain (corr.py:41-43, utils.py:61-62, ATen's un-normalise): the
+// corner and weight of one axis, for the plain lookup (corr.hip) and the tiled pyramid's backward (corr_lookup_tiled.hip) alike.
+__device__ __forceinline__ void tap_1d(float c, float inv_scale, int off, int n, int& i0, float& w1) {
+    const float cl = __fmul_rn(c, inv_scale);                 // coords / 2**i   (exact: power of two)
+    const float x = __fadd_rn(cl, (float)off);                // + delta
+    const float nm1 = (float)(n - 1);
+    const float g = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, x), nm1), 1.f);   // 2*x/(n-1) - 1
+    const float u = __fmul_rn(__fmul_rn(__fadd_rn(g, 1.f), 0.5f), nm1);  // ((g+1)/2)*(n-1)
+    const float f = floorf(u);
+    i0 = (int)f;
+    w1 = __fsub_rn(u, f);
+}
 
 struct CorrLayout {
     int h[4], w[4];        // plane sizes

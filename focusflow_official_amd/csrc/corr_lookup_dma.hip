@@ -34,18 +34,16 @@
 // (probe.hip / tools/proto/hbm_gather.hip) takes 13.9-14.6 us.
 #pragma clang fp contract(off)
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 #include "corr_layout.h"
 
 namespace {
 
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // LDS accesses by absolute 32-bit address (one wave per block: the dynamic LDS segment starts at 0)
-template <typename T>
-__device__ __forceinline__ T lds_ld(unsigned addr) { return *(__attribute__((address_space(3))) const T*)(unsigned long)addr; }
+using ff::lds_ld;
 template <typename T>
 __device__ __forceinline__ void lds_st(unsigned addr, T v) { *(__attribute__((address_space(3))) T*)(unsigned long)addr = v; }
 

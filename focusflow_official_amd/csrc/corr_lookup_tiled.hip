@@ -5,25 +5,13 @@
 // the separately rounded fp32 replay of corr.hip (tap indices bit-identical to the reference).
 #pragma clang fp contract(off)
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 #include "corr_layout.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// One separately-rounded replay of the sampler's coordinate chain (corr.py:41-43, utils.py:61-62, ATen's un-normalise).
-__device__ __forceinline__ void tap_1d(float c, float inv_scale, int off, int n, int& i0, float& w1) {
-    const float cl = __fmul_rn(c, inv_scale);
-    const float x = __fadd_rn(cl, (float)off);
-    const float nm1 = (float)(n - 1);
-    const float g = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, x), nm1), 1.f);
-    const float u = __fmul_rn(__fmul_rn(__fadd_rn(g, 1.f), 0.5f), nm1);
-    const float f = floorf(u);
-    i0 = (int)f;
-    w1 = __fsub_rn(u, f);
-}
+using ff::tap_1d;
 
 // ---------------------------------------------------------------------------
 // Lookup backward on tiled fp32 gradient planes: dlevel[l][q][y][x] += dout[q][k] * bilinear weight.

@@ -18,21 +18,15 @@
 //     the next chunk's loads in flight behind the current chunk's MFMAs (32 registers per buffer);
 //   * matrix form and LDS image are conv_dma.hip's / fusion_pair.hip's: v_mfma_f32_16x16x32_f16, A = weights, B = 16 pixels, LDS
 //     row = one pixel's 32-channel chunk [x0 | x1], its eight 16-byte slots XOR-swizzled by (pixel >> 1) & 7, lanes mapped to pixels
-//     through PI16.  Terms in conv_dma.hip's order (w0 x0, w1 x0, w0 x1), K in ascending chunks;
+//     through PI16.  Terms in ff::mfma16_terms' order (split_mfma.h: w0 x0, w1 x0, w0 x1), K in ascending chunks;
 //   * a lane's accumulator holds four consecutive output channels of one pixel: the epilogue - acc / 64 + bias as separately
 //     rounded operations - leaves as 16-byte stores straight from the registers (a wave's four stores fill 256 consecutive bytes
 //     of each of its 16 pixels).
 // hipcc-flags: -ffp-contract=off
 #include <algorithm>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-
-__device__ __forceinline__ int PI16(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9); }
 
 constexpr int C = 128;      // channels per input branch
 constexpr int COUT = 256;
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     f32x4 wa[NTW][2], wb[NTW][2];
     auto load_w = [&](int kc, f32x4 (&w)[NTW][2]) {          // [COUT / 16][NKC][term][lane][16 B]
 #pragma unroll
-        for (int v = 0; v < NTW; ++v) {
+        for (int v = 0; v < NTW; ++v) {       // (not ff::load_w_frag: with the offset as one shared value the compiler groups lane * 16 + 1024 differently - other address code)
             w[v][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16 + ((tile0 + v) * NKC + kc) * 2048, 0, 0));
             if (TERMS == 3) w[v][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16 + ((tile0 + v) * NKC + kc) * 2048 + 1024, 0, 0));
         }
@@ -115,12 +109,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int cc = (grp * 4) & 31, kcw = br * (C / 32) + ((grp * 4) >> 5);
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            ff::ff_f16x4 h0, h1;
+            f16x4 h0, h1;
             ff::split_pair4(val[j], h0, h1);
             const int px = j * PSTEP + pl, sw = (px >> 1) & 7;
             char* row = smem + kcw * PLANE + px * 128 + (cc & 7) * 2;
-            *reinterpret_cast<ff::ff_f16x4*>(row + (((cc >> 3) ^ sw) << 4)) = h0;
-            if (TERMS == 3) *reinterpret_cast<ff::ff_f16x4*>(row + (((4 + (cc >> 3)) ^ sw) << 4)) = h1;
+            *reinterpret_cast<f16x4*>(row + (((cc >> 3) ^ sw) << 4)) = h0;
+            if (TERMS == 3) *reinterpret_cast<f16x4*>(row + (((4 + (cc >> 3)) ^ sw) << 4)) = h1;
         }
     }
     __syncthreads();
@@ -131,25 +125,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int v = 0; v < NTW; ++v)
 #pragma unroll
         for (int g = 0; g < NPG; ++g) acc[v][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int pxl = PI16(i16), swl = (pxl >> 1) & 7;             // ((16 g + pxl) >> 1) & 7 == (pxl >> 1) & 7
+    const int pxl = ff::PI16(i16), swl = (pxl >> 1) & 7;             // ((16 g + pxl) >> 1) & 7 == (pxl >> 1) & 7
     const char* fa = smem + pxl * 128 + ((g16 ^ swl) << 4);
     const char* fb = smem + pxl * 128 + (((4 + g16) ^ swl) << 4);
     auto chunk = [&](int kc, const f32x4 (&w)[NTW][2]) {
 #pragma unroll
         for (int g = 0; g < NPG; ++g) {
             const f16x8 xa = *reinterpret_cast<const f16x8*>(fa + kc * PLANE + g * 2048);
-            f16x8 xb;
-            if (TERMS == 3) xb = *reinterpret_cast<const f16x8*>(fb + kc * PLANE + g * 2048);
+            const f16x8 xb = TERMS == 3 ? *reinterpret_cast<const f16x8*>(fb + kc * PLANE + g * 2048) : xa;
 #pragma unroll
-            for (int v = 0; v < NTW; ++v) {
-                const f16x8 w0 = __builtin_bit_cast(f16x8, w[v][0]);
-                acc[v][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xa, acc[v][g], 0, 0, 0);
-                if (TERMS == 3) {
-                    const f16x8 w1 = __builtin_bit_cast(f16x8, w[v][1]);
-                    acc[v][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, xa, acc[v][g], 0, 0, 0);
-                    acc[v][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xb, acc[v][g], 0, 0, 0);
-                }
-            }
+            for (int v = 0; v < NTW; ++v) ff::mfma16_terms<TERMS>(acc[v][g], w[v][0], w[v][1], xa, xb);
         }
     };
 #pragma unroll

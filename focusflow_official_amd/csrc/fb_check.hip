@@ -26,15 +26,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int MAX_ROWS = 4096;      // N of ff_fb_matches: the slots of a track table, the points of a detector
 
-// ff_tracks_advance's blend (tracks.hip), word for word
-__device__ __forceinline__ float blend(float f00, float f01, float f10, float f11, float fx, float fy) {
-    const float wx0 = __fsub_rn(1.f, fx);
-    const float top = __fadd_rn(__fmul_rn(wx0, f00), __fmul_rn(fx, f01));
-    const float bot = __fadd_rn(__fmul_rn(wx0, f10), __fmul_rn(fx, f11));
-    const float wy0 = __fsub_rn(1.f, fy);
-    return __fadd_rn(__fmul_rn(wy0, top), __fmul_rn(fy, bot));
-}
-
 // A field addressed by element strides, the frame at (left, top): one sample of it.
 struct Field {
     const float* p;
@@ -57,9 +48,9 @@ __device__ __forceinline__ bool round_trip(float X, float Y, float xt, float yt,
     const long long r0 = (long long)(y0 + top) * bw.ld_row, r1 = (long long)(y1 + top) * bw.ld_row;
     const long long c0 = (long long)(x0 + left) * bw.ld_col, c1 = (long long)(x1 + left) * bw.ld_col;
     const float* f = bw.p;
-    const float ub = blend(f[r0 + c0], f[r0 + c1], f[r1 + c0], f[r1 + c1], fx, fy);
+    const float ub = ff::blend(f[r0 + c0], f[r0 + c1], f[r1 + c0], f[r1 + c1], fx, fy);
     f += bw.ld_c;
-    const float vb = blend(f[r0 + c0], f[r0 + c1], f[r1 + c0], f[r1 + c1], fx, fy);
+    const float vb = ff::blend(f[r0 + c0], f[r0 + c1], f[r1 + c0], f[r1 + c1], fx, fy);
     const float du = __fsub_rn(__fadd_rn(xt, ub), X), dv = __fsub_rn(__fadd_rn(yt, vb), Y);
     err2 = __fadd_rn(__fmul_rn(du, du), __fmul_rn(dv, dv));
     const float fu = __fsub_rn(xt, X), fv = __fsub_rn(yt, Y);

@@ -8,6 +8,10 @@
 #include <cstdlib>
 #include "focusflow_hip.h"
 
+// the vector types of the split format's stores (split_mfma.h has the MFMA kernels' further ones, in the same spelling)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
 namespace ff {
 
 char* err_buf();  // thread-local, defined in api.hip
@@ -59,11 +63,19 @@ __device__ __forceinline__ void input_scale(const unsigned int* x_amax, float& x
         }
     }
 }
+// The pair of a value that is already on its scale (the loaders multiply by XSPLIT times ff::input_scale's factor first)
+__device__ __forceinline__ void split4(const f32x4 sv, f16x4& h0, f16x4& h1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const _Float16 a = (_Float16)sv[j];
+        h0[j] = a;
+        h1[j] = (_Float16)(sv[j] - (float)a);
+    }
+}
 // FF_FMT_SPLIT activations (focusflow_hip.h): the pair a convolution loader makes of an fp32 value, written by a producer.
 // 4 consecutive channels n4 .. n4 + 3 (n4 % 4 == 0) of one pixel -> two 8-byte stores into the pixel's 128-byte chunk.
-typedef _Float16 ff_f16x4 __attribute__((ext_vector_type(4)));
-typedef float ff_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split_pair4(const ff_f32x4 v, ff_f16x4& h0, ff_f16x4& h1) {
+// (Spelled out, not as split4(v * XSPLIT): tests/test_split_range.py pins these lines as the definition of the format.)
+__device__ __forceinline__ void split_pair4(const f32x4 v, f16x4& h0, f16x4& h1) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float sv = v[j] * XSPLIT;
@@ -74,13 +86,13 @@ __device__ __forceinline__ void split_pair4(const ff_f32x4 v, ff_f16x4& h0, ff_f
 }
 // pixel_row = base of the pixel's channels (fp32 addressing: y + pixel * ld); n4 = first of the four channels; nvalid = how
 // many of them exist (partial groups at Cout's edge store half by half)
-__device__ __forceinline__ void store_split4(float* pixel_row, int n4, const ff_f32x4 v, int nvalid = 4) {
-    ff_f16x4 h0, h1;
+__device__ __forceinline__ void store_split4(float* pixel_row, int n4, const f32x4 v, int nvalid = 4) {
+    f16x4 h0, h1;
     split_pair4(v, h0, h1);
     char* c = reinterpret_cast<char*>(pixel_row + (n4 & ~31)) + (n4 & 31) * 2;
     if (nvalid >= 4) {
-        *reinterpret_cast<ff_f16x4*>(c) = h0;
-        *reinterpret_cast<ff_f16x4*>(c + 64) = h1;
+        *reinterpret_cast<f16x4*>(c) = h0;
+        *reinterpret_cast<f16x4*>(c + 64) = h1;
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -134,6 +146,24 @@ inline const char* tune_env(const char*) { return nullptr; }
             ff_done_.fetch_or(ff_bit_, std::memory_order_relaxed);                                                               \
         }                                                                                                                        \
     } while (0)
+
+// ---- small exact helpers with more than one user (every operation separately rounded: no -ffp-contract dependence)
+// bilinear blend of four samples, the weights applied along x first (ff_tracks_advance, ff_fb_dense / ff_fb_matches: the
+// forward-backward check must re-sample the flow exactly as the tracker did)
+__device__ __forceinline__ float blend(float f00, float f01, float f10, float f11, float fx, float fy) {
+    const float wx0 = __fsub_rn(1.f, fx);
+    const float top = __fadd_rn(__fmul_rn(wx0, f00), __fmul_rn(fx, f01));
+    const float bot = __fadd_rn(__fmul_rn(wx0, f10), __fmul_rn(fx, f11));
+    const float wy0 = __fsub_rn(1.f, fy);
+    return __fadd_rn(__fmul_rn(wy0, top), __fmul_rn(fy, bot));
+}
+// ff_raft.py:142-145: x -> 2*(x/255) - 1, in that rounding order (input scaling, mask modes)
+__device__ __forceinline__ float scale255(float v) { return __fsub_rn(__fmul_rn(2.f, __fdiv_rn(v, 255.0f)), 1.0f); }
+// lowbias32: the RANSAC checks' draws, the memory probe's segment choice
+__device__ __forceinline__ unsigned mix(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
 
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

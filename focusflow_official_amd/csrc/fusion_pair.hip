@@ -16,20 +16,14 @@
 //     the pass and its write + re-read of the activation disappear (the normalised tensor has no other consumer).
 // Matrix form and LDS image are conv_dma.hip's: v_mfma_f32_16x16x32_f16, A = weights, B = 16 pixels; an LDS row is one
 // pixel's 32-channel chunk [x0: 32 fp16 | x1: 32 fp16], its eight 16-byte slots XOR-swizzled by (pixel >> 1) & 7, lanes
-// mapped to pixels through PI16 (bank-conflict-free fragment reads).  Terms in conv_dma.hip's order (w0 x0, w1 x0, w0 x1),
+// mapped to pixels through PI16 (bank-conflict-free fragment reads).  Terms in ff::mfma16_terms' order (split_mfma.h: w0 x0, w1 x0, w0 x1),
 // K in ascending chunks.  The epilogue is separately rounded operations: acc / 64 + bias, + residual.
 // hipcc-flags: -ffp-contract=off
 #include <algorithm>
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int PI16(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9); }
 
 struct FArgs {
     FFFusionPair p;
@@ -78,10 +72,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int v = 0; v < NTW; ++v) {
             const int tile = lb / 16 + v;
 #pragma unroll
-            for (int kc = 0; kc < NCH; ++kc) {
-                wr[v][kc][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16, (tile * NCH + kc) * 2048, 0));
-                if (TERMS == 3) wr[v][kc][TERMS == 3 ? 1 : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16, (tile * NCH + kc) * 2048 + 1024, 0));
-            }
+            for (int kc = 0; kc < NCH; ++kc) ff::load_w_frag<TERMS, true>(rw, lane * 16, (tile * NCH + kc) * 2048, wr[v][kc]);
         }
     };
     if (WRES) load_w();
@@ -146,11 +137,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 if (!loader) continue;
-                ff::ff_f16x4 h0, h1;
+                f16x4 h0, h1;
                 ff::split_pair4(val[br][j], h0, h1);
                 const int jx = (PSTEP == 8 && (j & 1)) ? 64 : 0;
-                *reinterpret_cast<ff::ff_f16x4*>(smem + br * NCH * PLANE + j * PSTEP * 128 + (wofs0 ^ jx)) = h0;
-                if (TERMS == 3) *reinterpret_cast<ff::ff_f16x4*>(smem + br * NCH * PLANE + j * PSTEP * 128 + (wofs1 ^ jx)) = h1;
+                *reinterpret_cast<f16x4*>(smem + br * NCH * PLANE + j * PSTEP * 128 + (wofs0 ^ jx)) = h0;
+                if (TERMS == 3) *reinterpret_cast<f16x4*>(smem + br * NCH * PLANE + j * PSTEP * 128 + (wofs1 ^ jx)) = h1;
             }
         if (!WRES) load_w();
         __syncthreads();
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int g = 0; g < NPG; ++g) acc[v][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
         {
-            const int pxl = PI16(i16), swl = (pxl >> 1) & 7;             // ((16 g + pxl) >> 1) & 7 == (pxl >> 1) & 7
+            const int pxl = ff::PI16(i16), swl = (pxl >> 1) & 7;             // ((16 g + pxl) >> 1) & 7 == (pxl >> 1) & 7
             const char* fa = smem + ib * NCH * PLANE + pxl * 128 + ((g16 ^ swl) << 4);
             const char* fb = smem + ib * NCH * PLANE + pxl * 128 + (((4 + g16) ^ swl) << 4);
 #pragma unroll
@@ -169,24 +160,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int g = 0; g < NPG; ++g) {
                     const f16x8 xa = *reinterpret_cast<const f16x8*>(fa + kc * PLANE + g * 2048);
-                    f16x8 xb;
-                    if (TERMS == 3) xb = *reinterpret_cast<const f16x8*>(fb + kc * PLANE + g * 2048);
+                    const f16x8 xb = TERMS == 3 ? *reinterpret_cast<const f16x8*>(fb + kc * PLANE + g * 2048) : xa;
 #pragma unroll
-                    for (int v = 0; v < NTW; ++v) {
-                        const f16x8 w0 = __builtin_bit_cast(f16x8, wr[v][kc][0]);
-                        acc[v][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xa, acc[v][g], 0, 0, 0);
-                        if (TERMS == 3) {
-                            const f16x8 w1 = __builtin_bit_cast(f16x8, wr[v][kc][TERMS == 3 ? 1 : 0]);
-                            acc[v][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, xa, acc[v][g], 0, 0, 0);
-                            acc[v][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xb, acc[v][g], 0, 0, 0);
-                        }
-                    }
+                    for (int v = 0; v < NTW; ++v) ff::mfma16_terms<TERMS>(acc[v][g], wr[v][kc][0], wr[v][kc][TERMS == 3 ? 1 : 0], xa, xb);
                 }
             }
         }
         __syncthreads();          // everybody is done reading the operand image: the staging rows take its place
         {
-            char* st = smem + PI16(i16) * SROW + (nb + g16 * 4) * 4;
+            char* st = smem + ff::PI16(i16) * SROW + (nb + g16 * 4) * 4;
 #pragma unroll
             for (int v = 0; v < NTW; ++v)
 #pragma unroll
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 // (vector offset only: a 16-byte buffer store with a scalar offset register followed at once by a write of its
                 // data registers - the next pass's v_pk_add_f32 - lost the race on gfx950: the fourth dword of pass j left as
                 // pass j + 1's.  No scalar offset, no hazard.)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o), ry[br], voff + tb + j * (NACT * 16), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ry[br], voff + tb + j * (NACT * 16), 0, 0);
             }
         __syncthreads();          // the staging rows are read: the next tile's operand image may overwrite them
     }

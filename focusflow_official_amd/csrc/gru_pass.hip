@@ -19,28 +19,12 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char* lds_ptr_t;
-
-__device__ __forceinline__ int PI16(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9); }
-__device__ __forceinline__ f16x8 lds_ld16(unsigned addr) { return *(__attribute__((address_space(3))) const f16x8*)(unsigned long)addr; }
-constexpr unsigned OOB = 0x7fffffffu;
-
-__device__ __forceinline__ void dma_piece(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned dst, unsigned soff) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(rs), "s"(dst), "s"(soff)
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+using ff::OOB;
+using ff::lds_ld16;
 
 struct GArgs {
     const float* hs;   int hs_ld;      // state, split-pair [B][H][W][128]
@@ -95,7 +79,7 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
     const int py0 = y0 - (DIR == 1 ? 4 : 0), px0 = x0 - (DIR == 0 ? 4 : 0);      // patch origin
     const int ry0 = y0 - (DIR == 1 ? 2 : 0), rx0 = x0 - (DIR == 0 ? 2 : 0);      // r-region origin
     const long long pix_total = (long long)a.B * H * W;
-    const int i16 = lane & 15, g16 = lane >> 4, pcol = PI16(i16);
+    const int i16 = lane & 15, g16 = lane >> 4, pcol = ff::PI16(i16);
 
     // ---- DMA roles (8 waves): piece pc = wave + 8 j covers patch rows 8 pc .. 8 pc + 7
     int ppix[NPP];
@@ -116,8 +100,8 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
         for (int j = 0; j < NPP; ++j) {
             if ((wave + 8 * j) < NPIECE) {
                 const unsigned voff = ppix[j] >= 0 ? __umul24((unsigned)(ppix[j] >> 7), (unsigned)ldb) + (unsigned)(ppix[j] & 127) : OOB;
-                if (motion) dma_piece(voff, rs_m, lds0 + buf * PBYTES + (wave + 8 * j) * 1024, soff);
-                else dma_piece(voff, rs_h, lds0 + buf * PBYTES + (wave + 8 * j) * 1024, soff);
+                if (motion) ff::dma_piece<false>(voff, rs_m, lds0 + buf * PBYTES + (wave + 8 * j) * 1024, soff);
+                else ff::dma_piece<false>(voff, rs_h, lds0 + buf * PBYTES + (wave + 8 * j) * 1024, soff);
             }
         }
     };
@@ -130,16 +114,13 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
     auto issue_w1 = [&](auto set_tag, int kc) {
         constexpr int S = decltype(set_tag)::value;
         const int soff = kc * 2048;
-        wz[S][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_wzr, woff_z, soff, 0));
-        if (TERMS == 3) wz[S][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_wzr, woff_z + 1024, soff, 0));
-        wr[S][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_wzr, woff_r, soff, 0));
-        if (TERMS == 3) wr[S][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_wzr, woff_r + 1024, soff, 0));
+        ff::load_w_frag<TERMS>(rs_wzr, woff_z, soff, wz[S]);
+        ff::load_w_frag<TERMS>(rs_wzr, woff_r, soff, wr[S]);
     };
     auto issue_w2 = [&](auto set_tag, int kc) {
         constexpr int S = decltype(set_tag)::value;
         const int soff = kc * 2048;
-        wq_[S][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_wq, woff_q, soff, 0));
-        if (TERMS == 3) wq_[S][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_wq, woff_q + 1024, soff, 0));
+        ff::load_w_frag<TERMS>(rs_wq, woff_q, soff, wq_[S]);
     };
 
     // ---- this lane's pixel in the r tiles: regular tile j = r-region row j (DIR 1) / row j, columns 2 + .. (DIR 0); halo tile k
@@ -182,7 +163,7 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
         constexpr int T = decltype(t_tag)::value, CUR = decltype(set_tag)::value, NXT = CUR ^ 1;
         const bool more = c + 1 < 2 * NCH;
         if constexpr (T == 0) {
-            wait_vm<NWL1>();
+            ff::wait_vm<NWL1>();
             __builtin_amdgcn_s_barrier();
         }
         issue_w1(std::integral_constant<int, NXT>{}, T + 1 < NT ? (T + 1) * (2 * NCH) + c : (more ? c + 1 : 0));
@@ -195,7 +176,7 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
             constexpr int LO = decltype(lo_tag)::value, HI = decltype(hi_tag)::value;
 #pragma unroll
             for (int j = LO; j < HI; ++j) {
-                f16x8 xa, xb;
+                f16x8 xa, xb = {};      // (xb: unused when TERMS == 1)
                 if (j < NREG) {
                     xa = lds_ld16(xa0 + j * PW * 128);
                     if (TERMS == 3) xb = lds_ld16(xa1 + j * PW * 128);
@@ -206,22 +187,8 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
                     xa = lds_ld16(hb + ((g16 ^ hs_) << 4));
                     if (TERMS == 3) xb = lds_ld16(hb + (((4 + g16) ^ hs_) << 4));
                 }
-                const f16x8 r0 = __builtin_bit_cast(f16x8, wr[CUR][0]);
-                ar[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r0, xa, ar[j], 0, 0, 0);
-                if (TERMS == 3) {
-                    const f16x8 r1 = __builtin_bit_cast(f16x8, wr[CUR][1]);
-                    ar[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r1, xa, ar[j], 0, 0, 0);
-                    ar[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r0, xb, ar[j], 0, 0, 0);
-                }
-                if (j >= ZOFF && j < ZOFF + TH) {        // the tile's own pixels: z from the same fragments
-                    const f16x8 z0 = __builtin_bit_cast(f16x8, wz[CUR][0]);
-                    az[j - ZOFF] = __builtin_amdgcn_mfma_f32_16x16x32_f16(z0, xa, az[j - ZOFF], 0, 0, 0);
-                    if (TERMS == 3) {
-                        const f16x8 z1 = __builtin_bit_cast(f16x8, wz[CUR][1]);
-                        az[j - ZOFF] = __builtin_amdgcn_mfma_f32_16x16x32_f16(z1, xa, az[j - ZOFF], 0, 0, 0);
-                        az[j - ZOFF] = __builtin_amdgcn_mfma_f32_16x16x32_f16(z0, xb, az[j - ZOFF], 0, 0, 0);
-                    }
-                }
+                ff::mfma16_terms<TERMS>(ar[j], wr[CUR][0], wr[CUR][1], xa, xb);
+                if (j >= ZOFF && j < ZOFF + TH) ff::mfma16_terms<TERMS>(az[j - ZOFF], wz[CUR][0], wz[CUR][1], xa, xb);        // the tile's own pixels: z from the same fragments
             }
         };
         if constexpr (T == 0) {
@@ -305,11 +272,11 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
             if (a.sv_r && j >= ZOFF && j - ZOFF < TH && j < NREG && rin[j])      // r tile u + ZOFF sits on the output tile's row u (the same pixels as z and q)
                 *reinterpret_cast<f32x4*>(a.sv_r + (((long long)bimg * H + (ry0 + rrow[j])) * W + (rx0 + rcol[j])) * a.sv_ld + cw) = rv;
             if (!live[j]) continue;
-            ff::ff_f16x4 h0, h1;
+            f16x4 h0, h1;
             ff::split_pair4(t, h0, h1);
             const unsigned adr = rh0 + chunk * RPLANE + (unsigned)((rrow[j] * RW + rcol[j]) * 128) + (((unsigned)slot ^ (unsigned)((rcol[j] >> 1) & 7)) << 4) + half8;
-            *(__attribute__((address_space(3))) ff::ff_f16x4*)(unsigned long)adr = h0;
-            if (TERMS == 3) *(__attribute__((address_space(3))) ff::ff_f16x4*)(unsigned long)(adr ^ 64) = h1;
+            *(__attribute__((address_space(3))) f16x4*)(unsigned long)adr = h0;
+            if (TERMS == 3) *(__attribute__((address_space(3))) f16x4*)(unsigned long)(adr ^ 64) = h1;
         }
     }
     __syncthreads();            // r * h complete for every wave (lgkmcnt + barrier; the vmcnt(0) also lands the motion patch and q's first weights)
@@ -324,7 +291,7 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
         const bool mo = c >= NCH;                       // chunks 0..3: r * h (resident planes), 4..7: motion (patch buffers (c & 1))
         if constexpr (T == 0) {
             if (mo && c > NCH) {                        // (chunk 4's patch was landed by the __syncthreads above)
-                wait_vm<NWL2>();
+                ff::wait_vm<NWL2>();
                 __builtin_amdgcn_s_barrier();
             }
         }
@@ -346,15 +313,8 @@ __global__ __launch_bounds__(512) void gru_pass_kernel(const GArgs a) {
 #pragma unroll
             for (int u = LO; u < HI; ++u) {
                 const f16x8 xa = lds_ld16(xa0 + u * rstride);
-                f16x8 xb;
-                if (TERMS == 3) xb = lds_ld16(xa1 + u * rstride);
-                const f16x8 q0 = __builtin_bit_cast(f16x8, wq_[CUR][0]);
-                aq[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q0, xa, aq[u], 0, 0, 0);
-                if (TERMS == 3) {
-                    const f16x8 q1 = __builtin_bit_cast(f16x8, wq_[CUR][1]);
-                    aq[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q1, xa, aq[u], 0, 0, 0);
-                    aq[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q0, xb, aq[u], 0, 0, 0);
-                }
+                const f16x8 xb = TERMS == 3 ? lds_ld16(xa1 + u * rstride) : xa;
+                ff::mfma16_terms<TERMS>(aq[u], wq_[CUR][0], wq_[CUR][1], xa, xb);
             }
         };
         if constexpr (T == 0) {

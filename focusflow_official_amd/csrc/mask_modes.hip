@@ -14,9 +14,7 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float scale255(float v) { return __fsub_rn(__fmul_rn(2.f, __fdiv_rn(v, 255.0f)), 1.0f); }
+using ff::scale255;
 
 // phase 1: tmp[b,y,x] = sum_k table[k] * src(mask)[y+dy, x+dx]  (src = mask or mask/255), global max
 __global__ void mask_conv_kernel(const float* __restrict__ mask, const float* __restrict__ table, int ks, float pre_div,

@@ -16,16 +16,10 @@
 // stage was exposed: 46 us), the activations are split on the way in.
 // Wave (wp, ws): pixels 32 wp .. + 31, sub-pixels 32 ws .. + 31 of every k: 9 accumulators = 144 registers.
 #include <cstdlib>
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int NCH = 576, KIN = 256, PXB = 96, NTHR = 384;
 constexpr int WROWS = NCH * 64;                 // weight image of a stage: 576 rows x 64 B
@@ -140,7 +134,7 @@ __global__ __launch_bounds__(NTHR) void mask_upsample_kernel(const MUArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const f16x8 w0 = *reinterpret_cast<const f16x8*>(sb + ca0 + k * 4096);
-            acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, x0, acc[k], 0, 0, 0);
+            acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, x0, acc[k], 0, 0, 0);      // (ff::mfma32_terms' order written out: w1 is read BETWEEN the first term and the other two)
             if (TERMS == 3) {
                 const f16x8 w1 = *reinterpret_cast<const f16x8*>(sb + ca1 + k * 4096);
                 acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, x0, acc[k], 0, 0, 0);
@@ -305,7 +299,7 @@ __global__ __launch_bounds__(NTHR12) void mask_upsample12_kernel(const MUArgs a)
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             const f16x8 w0 = *reinterpret_cast<const f16x8*>(sb + ca0 + j * 8192);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, x0, acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, x0, acc[j], 0, 0, 0);      // (ff::mfma32_terms' order written out: w1 is read BETWEEN the first term and the other two)
             if (TERMS == 3) {
                 const f16x8 w1 = *reinterpret_cast<const f16x8*>(sb + ca1 + j * 8192);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, x0, acc[j], 0, 0, 0);

@@ -4,16 +4,11 @@
 // (FF_TIME_PROBE).  bench.py runs it next to the lookup so that "fraction of the 8 TB/s peak" has a measured companion:
 // what this part delivers to ANY kernel that moves that many bytes in one launch.  tools/proto/hbm_gather.hip is the
 // stand-alone version with more patterns.
-#include "ff_common.h"
+#include "split_mfma.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned mix(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
+using ff::mix;
 
 __global__ __launch_bounds__(64) void probe_kernel(const char* src, unsigned long long nseg, unsigned seg, int trips, char* dst, unsigned salt,
                                                    unsigned* sink) {

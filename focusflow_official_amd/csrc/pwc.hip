@@ -21,7 +21,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 16, R = 4, HH = TH + 2 * R, HW = TW + 2 * R;   // tile + halo
 constexpr int CK = 16, LDP = 20;                                         // channels per chunk, padded LDS pitch

@@ -20,14 +20,7 @@ struct Frame {
     float cx, cy, s;                // xn = (x - cx) s
 };
 
-__device__ __forceinline__ unsigned mix(unsigned x) {      // lowbias32
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
+using ff::mix;
 
 __device__ __forceinline__ bool finite4(const float4 m) { return isfinite(m.x) && isfinite(m.y) && isfinite(m.z) && isfinite(m.w); }
 __device__ __forceinline__ bool candidate(const float4 m, unsigned char valid) { return valid && m.x >= 0.f && finite4(m); }

@@ -167,14 +167,6 @@ __global__ void __launch_bounds__(THREADS) mask_scatter_kernel(const float2* __r
     mask[(long long)(r / N) * H * W + (long long)y * W + x] = 255.f;
 }
 
-__device__ __forceinline__ float blend(float f00, float f01, float f10, float f11, float fx, float fy) {
-    const float wx0 = __fsub_rn(1.f, fx);
-    const float top = __fadd_rn(__fmul_rn(wx0, f00), __fmul_rn(fx, f01));
-    const float bot = __fadd_rn(__fmul_rn(wx0, f10), __fmul_rn(fx, f11));
-    const float wy0 = __fsub_rn(1.f, fy);
-    return __fadd_rn(__fmul_rn(wy0, top), __fmul_rn(fy, bot));
-}
-
 // one thread per (b, slot)
 __global__ void __launch_bounds__(THREADS) advance_kernel(float2* __restrict__ pos, long long* __restrict__ ids, int* __restrict__ age, int N,
                                                           const float* __restrict__ flow, long long fb, long long fc, long long fy_, long long fx_,
@@ -196,8 +188,8 @@ __global__ void __launch_bounds__(THREADS) advance_kernel(float2* __restrict__ p
         const float* f = flow + (r / N) * fb;
         const long long o00 = (long long)(y0 + top) * fy_ + (long long)(x0 + left) * fx_, o01 = (long long)(y0 + top) * fy_ + (long long)(x1 + left) * fx_;
         const long long o10 = (long long)(y1 + top) * fy_ + (long long)(x0 + left) * fx_, o11 = (long long)(y1 + top) * fy_ + (long long)(x1 + left) * fx_;
-        const float u = blend(f[o00], f[o01], f[o10], f[o11], fx, fy);
-        const float v = blend(f[fc + o00], f[fc + o01], f[fc + o10], f[fc + o11], fx, fy);
+        const float u = ff::blend(f[o00], f[o01], f[o10], f[o11], fx, fy);
+        const float v = ff::blend(f[fc + o00], f[fc + o01], f[fc + o10], f[fc + o11], fx, fy);
         const float tx = __fadd_rn(p.x, u), ty = __fadd_rn(p.y, v);
         m = make_float4(p.x, p.y, tx, ty);
         ok = tx >= 0.f && tx <= (float)(W - 1) && ty >= 0.f && ty <= (float)(H - 1);      // (NaN: 0)

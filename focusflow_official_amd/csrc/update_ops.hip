@@ -6,10 +6,7 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ff_raft.py:142-145: x -> 2*(x/255) - 1, in that rounding order.
-__device__ __forceinline__ float scale255(float v) { return __fsub_rn(__fmul_rn(2.f, __fdiv_rn(v, 255.0f)), 1.0f); }
+using ff::scale255;
 
 __global__ void prep_input_kernel(const float* __restrict__ src, int src_c, float fill, float* __restrict__ dst,
                                   int B, int HW) {
@@ -60,7 +57,7 @@ __global__ void split_copy_kernel(const float* __restrict__ src, int src_ld, flo
             ff::store_split4(dst + p * dst_ld, n4, v);
         } else {
             const char* c = reinterpret_cast<const char*>(src + p * src_ld + (n4 & ~31)) + (n4 & 31) * 2;
-            const ff::ff_f16x4 h0 = *reinterpret_cast<const ff::ff_f16x4*>(c), h1 = *reinterpret_cast<const ff::ff_f16x4*>(c + 64);
+            const f16x4 h0 = *reinterpret_cast<const f16x4*>(c), h1 = *reinterpret_cast<const f16x4*>(c + 64);
             f32x4 v;
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = ((float)h0[j] + (float)h1[j]) * 0.25f;
