@@ -145,6 +145,9 @@ _SIGS = {
     "ff_homography_ransac": [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, _fp, C.c_int, _fp, _fp,
                              _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _ll, _fp],
     "ff_homography_residual": [_fp, _ll, _ll, _ll, _ll, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp],
+    "ff_flow_rad_max": [_fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp],
+    "ff_flow_to_image": [_fp, _ll, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_double, C.c_float,
+                         _fp, _ll, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _ll, _ll, _ll, _ll, _fp],
     "ff_coords_step": [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp],
     "ff_gru_pass": [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int,
                     C.c_int, C.c_int, C.c_int, _fp],

@@ -1,4 +1,4 @@
-"""Video sessions at the application's boundary: raw uint8 frames in, key-point matches out.
+"""Video sessions at the application's boundary: raw uint8 frames in, key-point matches and flow images out.
 
 `warm_start.FlowSequence` takes padded fp32 image pairs and returns the dense padded field.  A video application has
 neither: a decoder hands it one uint8 HWC frame at a time, whose height is usually no multiple of 8 (540, 1080), and a
@@ -53,6 +53,16 @@ where it does (F is under-determined there), and with Homography.dense writes th
     res.hom.H, res.hom.ok, res.hom.planar    # (B,3,3) fp32 in pixel coordinates, (x', y', 1) ~ H (x, y, 1); (B) uint8; (B) uint8
     res.hom.status, res.hom.dist2            # per row of res.matches, as res.epi's; the squared transfer error in px^2
     res.hom.residual                         # dense=True: (B,H,W) fp32 px^2, -1 without a verdict; else None
+
+With render=True (or render=Render(max_flow, clip_flow, order, layout, occluded, backward)) the step also paints the flow
+(csrc/flow_viz.hip: the Middlebury colour wheel of the reference's flow_viz.py): bytes in, bytes out, 3 B per pixel ready for an
+encoder or a window instead of the 8 B of the field and a numpy pass over them.
+
+    seq = FrameSequence(model, raft_iters=12, fb=True, render=Render(max_flow=24.0, occluded=(255, 0, 255)))
+    res.view.image                           # uint8 (B,H,W,3) / (B,3,H,W), in the layout and channel order of the session's
+                                             # frames unless Render says otherwise; occluded pixels (res.fb.occluded) painted
+    res.view.rad_max                         # (B) fp32: the maximum magnitude each frame was scaled by; None with max_flow
+    res.view.image_bw                        # backward=True: the image of res.fb.flow_bw; else None
 """
 from operator import itemgetter
 from typing import NamedTuple, Optional
@@ -102,6 +112,52 @@ class FBResult(NamedTuple):
     status: Optional[torch.Tensor]
 
 
+class Render(NamedTuple):
+    """The flow images of a session (FrameSequence(render=...)).  max_flow: a fixed scale (finite, > 0) instead of each frame's
+    own maximum magnitude, so that the colours do not pump from frame to frame; clip_flow (>= 0): np.clip(flow, 0, clip_flow) first,
+    as the reference's flow_to_image does it; order ('rgb' / 'bgr') and layout ('hwc' / 'chw'): None means the session's own, so
+    a session fed BGR HWC frames gets BGR HWC images; occluded: None, or the (r, g, b) triple of 0 .. 255 that the pixels of the
+    forward-backward check's occlusion map are painted with (needs fb=); backward: also render the backward flow (needs fb=)."""
+    max_flow: Optional[float] = None
+    clip_flow: Optional[float] = None
+    order: Optional[str] = None
+    layout: Optional[str] = None
+    occluded: Optional[tuple] = None
+    backward: bool = False
+
+
+def as_render(render) -> Optional[Render]:
+    """None / False -> None, True -> the defaults, a Render -> itself, checked; anything else is a ValueError."""
+    if render is None or render is False:
+        return None
+    if render is True:
+        return Render()
+    if not isinstance(render, Render):
+        raise ValueError(f"render: True or a frames.Render(max_flow, clip_flow, order, layout, occluded, backward) expected, got {type(render).__name__}")
+    if render.max_flow is not None and not (render.max_flow > 0 and render.max_flow != float("inf")):
+        raise ValueError(f"render: max_flow={render.max_flow}: None (every frame's own maximum) or a finite value > 0")
+    if render.clip_flow is not None and not render.clip_flow >= 0:
+        raise ValueError(f"render: clip_flow={render.clip_flow}: None or a value >= 0")
+    if render.order not in (None, "rgb", "bgr"):
+        raise ValueError(f"render: order={render.order!r}: None (the session's), 'rgb' or 'bgr'")
+    if render.layout not in (None, "hwc", "chw"):
+        raise ValueError(f"render: layout={render.layout!r}: None (the session's), 'hwc' or 'chw'")
+    if render.occluded is not None:
+        c = render.occluded
+        if not isinstance(c, (tuple, list)) or len(c) != 3 or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x <= 255 for x in c):
+            raise ValueError(f"render: occluded={c!r}: None or an (r, g, b) triple of integers 0 .. 255")
+    return render
+
+
+class RenderResult(NamedTuple):
+    """What a pair adds to a FrameResult in a session with render=: the flow image, uint8 (B,H,W,3) or (B,3,H,W); the maximum
+    magnitude every sample's frame was scaled by, (B) fp32 (None with Render.max_flow); with Render.backward the image of the
+    backward flow (its own maximum, no occlusion paint), else None.  Session buffers: valid until the next push."""
+    image: torch.Tensor
+    rad_max: Optional[torch.Tensor]
+    image_bw: Optional[torch.Tensor]
+
+
 class FrameResult(tuple):
     """(flow_low, flow_up, matches, valid, count): the named tuple a push returns.  In tracks mode it is a TrackedFrameResult, the
     same with a sixth item `tracks` (a tracks.TrackResult); in a session with fb= it carries a trailing item `fb` (an FBResult)
@@ -110,14 +166,17 @@ class FrameResult(tuple):
     epipolar= gets the shape it would have without, plus a last item `epi` (a geometry.EpiResult): Epi-, TrackedEpi-, CheckedEpi-
     and TrackedCheckedEpiFrameResult; `.epi` is None in the four shapes without.  A session with homography= likewise gets the
     shape it would have without, plus a last item `hom` (a geometry.HomResult): each of the eight has a subclass whose name
-    puts Hom before FrameResult (HomFrameResult .. TrackedCheckedEpiHomFrameResult); `.hom` is None in the eight without.  The
-    fifteen subclasses are generated from one table (_OPTIONAL), and all sixteen behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
+    puts Hom before FrameResult (HomFrameResult .. TrackedCheckedEpiHomFrameResult); `.hom` is None in the eight without.  A
+    session with render= gets, again, the shape it would have without plus a last item `view` (a RenderResult): each of the sixteen
+    has a subclass whose name puts Rendered before FrameResult (RenderedFrameResult .. TrackedCheckedEpiHomRenderedFrameResult);
+    `.view` is None in the sixteen without.  The thirty-one subclasses are generated from one table (_OPTIONAL), and all
+    thirty-two behave as typing.NamedTuple classes do: `_fields`, `_asdict()`, `_replace()`, `_make()`, copy, deepcopy and pickle."""
     __slots__ = ()
     _fields = ("flow_low", "flow_up", "matches", "valid", "count")
 
     def __new__(cls, flow_low, flow_up, matches, valid, count, tracks: Optional[TrackResult] = None, fb: Optional[FBResult] = None,
-                epi: Optional[EpiResult] = None, hom: Optional[HomResult] = None):
-        extras = {f: x for f, x in zip(_OPTIONAL_FIELDS, (tracks, fb, epi, hom)) if x is not None}
+                epi: Optional[EpiResult] = None, hom: Optional[HomResult] = None, view: Optional[RenderResult] = None):
+        extras = {f: x for f, x in zip(_OPTIONAL_FIELDS, (tracks, fb, epi, hom, view)) if x is not None}
         return tuple.__new__(_SHAPES[tuple(extras)], (flow_low, flow_up, matches, valid, count, *extras.values()))
 
     flow_low = property(itemgetter(0))
@@ -125,17 +184,17 @@ class FrameResult(tuple):
     matches = property(itemgetter(2))
     valid = property(itemgetter(3))
     count = property(itemgetter(4))
-    tracks = fb = epi = hom = property(lambda self: None)      # (a shape that has the item answers with it: _shape)
+    tracks = fb = epi = hom = view = property(lambda self: None)      # (a shape that has the item answers with it: _shape)
 
     def __getnewargs__(self):      # (copy, deepcopy and pickle rebuild through __new__, item by item)
         return tuple(self[:5]) + tuple(getattr(self, f) for f in _OPTIONAL_FIELDS)
 
     @classmethod
     def _make(cls, iterable):
-        """From the items of any of the sixteen shapes; an item behind the fifth is `fb` if it is an FBResult, `epi` if it is an
-        EpiResult, `hom` if it is a HomResult, else `tracks`."""
+        """From the items of any of the thirty-two shapes; an item behind the fifth is `fb` if it is an FBResult, `epi` if it is an
+        EpiResult, `hom` if it is a HomResult, `view` if it is a RenderResult, else `tracks`."""
         items = tuple(iterable)
-        if len(items) <= 5 or len(items) > 9:
+        if len(items) <= 5 or len(items) > 10:
             return FrameResult(*items)      # (too few or too many: the TypeError of __new__)
         extras = {}
         for x in items[5:]:
@@ -160,16 +219,17 @@ class FrameResult(tuple):
 
 # The optional items behind the fifth, in their order: the field, what its presence puts into the class name, the type that
 # identifies it in _make.  The next check's result is one more row (and one more keyword of __new__).
-_OPTIONAL = (("tracks", "Tracked", TrackResult), ("fb", "Checked", FBResult), ("epi", "Epi", EpiResult), ("hom", "Hom", HomResult))
+_OPTIONAL = (("tracks", "Tracked", TrackResult), ("fb", "Checked", FBResult), ("epi", "Epi", EpiResult), ("hom", "Hom", HomResult),
+             ("view", "Rendered", RenderResult))
 _OPTIONAL_FIELDS = tuple(row[0] for row in _OPTIONAL)
 
 
 def _shape(rows):
     """The class of a FrameResult with the optional items `rows` (a non-empty selection from _OPTIONAL, in its order).  A shape
-    with `hom` is a subclass of the shape without, so `tracks`, `fb` and `epi` stay where they are; every other one is a direct
-    subclass of FrameResult."""
+    whose last item is `hom` or `view` is a subclass of the shape without that item, so the items before it stay where they
+    are; every other one is a direct subclass of FrameResult."""
     fields, name = tuple(r[0] for r in rows), "".join(r[1] for r in rows) + "FrameResult"
-    base = _SHAPES[fields[:-1]] if fields[-1] == "hom" else FrameResult
+    base = _SHAPES[fields[:-1]] if fields[-1] in ("hom", "view") else FrameResult
     body = {"__slots__": (), "__module__": __name__, "__qualname__": name, "_fields": FrameResult._fields + fields,
             "__doc__": f"A FrameResult of a session with {', '.join(fields)}: {5 + len(fields)} items, those last.  Made by "
                        f"FrameResult(..., {', '.join(f + '=...' for f in fields)})."}
@@ -177,9 +237,9 @@ def _shape(rows):
     return type(name, (base,), body)
 
 
-# the items present -> the shape.  All sixteen are module attributes: pickle finds them by name
+# the items present -> the shape.  All thirty-two are module attributes: pickle finds them by name
 _SHAPES = {(): FrameResult}
-for _n in range(1, 2 ** len(_OPTIONAL)):      # (`hom` is the highest bit: a shape without it is made before the one with it)
+for _n in range(1, 2 ** len(_OPTIONAL)):      # (`hom` and `view` are the highest bits: a shape without its last item is made before the one with it)
     _rows = [row for _i, row in enumerate(_OPTIONAL) if _n >> _i & 1]
     _cls = _shape(_rows)
     _SHAPES[_cls._fields[5:]] = globals()[_cls.__name__] = _cls
@@ -246,12 +306,19 @@ class FrameSequence:
     writes what is left of the cropped flow_up once H's motion is removed.  The check has an epoch word of its own, kept as the
     epipolar one is.  The result then carries `hom` (a geometry.HomResult) as its last item.
 
+    render=True or render=Render(...): behind the forward-backward check the step paints the flow (ops.flow_to_image on the padded
+    flow_up with the session's left, top, h, w, so the maximum a frame is scaled by is that of the frame, not of the padding)
+    into a static uint8 buffer of the session's layout and channel order (or Render's): two launches, one with Render.max_flow.
+    With Render.occluded the occlusion map of fb= is painted over it, with Render.backward the backward flow is rendered too.
+    Rendering only reads: every other item of the result is what the same session gives without render=.  The result then
+    carries `view` (a RenderResult) as its last item.
+
     The tensors of a result are the session's static buffers: valid until the next push.  A frame in pinned host memory is
     read by an asynchronous copy: leave it alone until work enqueued after the push has finished (the event a consumer
     waits for anyway before it reads the matches)."""
 
     def __init__(self, model, raft_iters=12, warm_start=True, graph=True, keypoints=None, layout="hwc", order="rgb", pad_mode="sintel",
-                 tracks=None, fb=None, epipolar=None, homography=None):
+                 tracks=None, fb=None, epipolar=None, homography=None, render=None):
         if not isinstance(model, FF_RAFT_FUSION):
             raise ValueError(f"model: FrameSequence drives FF_RAFT_FUSION, whose forward takes flow_init; {type(model).__name__} "
                              "(FF_PWCNET has no flow_init) runs pair by pair through graph.GraphedForward")
@@ -274,6 +341,11 @@ class FrameSequence:
         for word, config in (("epipolar", self.epipolar), ("homography", self.homography)):
             if config is not None and keypoints is None:
                 raise ValueError(f"{word}: the check judges the matches of key points: give the session keypoints=GoodFeatures(...)")
+        self.render = as_render(render)      # the Render of the session; None: no flow images
+        if self.render is not None and self.fb is None:
+            for word, on in (("occluded", self.render.occluded is not None), ("backward", self.render.backward)):
+                if on:
+                    raise ValueError(f"render: {word}= paints what the forward-backward check computes: give the session fb=True")
         self._reads_mask = getattr(model, "mask_modal", None) is not None
         self._require_eval()
         self._key = None
@@ -290,6 +362,7 @@ class FrameSequence:
         self._fb_mask = self._fb_mask_det = self._fb_init = self._guard_words_bw = None
         self._epi = None      # the geometry.EpipolarCheck: workspace, outputs, the epoch word
         self._hom = self._hom_valid = None      # the geometry.HomographyCheck: the same, and the dense residual; the copy of `valid` it judges without cull
+        self._view = self._view_bw = self._rad_max = self._rad_max_bw = None      # the flow images and the maxima they were scaled by
         self._frames = 0      # frames of the running sequence that have been ingested
 
     @property
@@ -399,6 +472,15 @@ class FrameSequence:
             self._hom.prepare(b, rows, device, h, w)
             if not self.homography.cull:
                 self._hom_valid = torch.zeros((b, rows), dtype=torch.uint8, device=device)
+        if self.render is not None:
+            shape = (b, h, w, 3) if (self.render.layout or self.layout) == "hwc" else (b, 3, h, w)
+            self._view = torch.zeros(shape, dtype=torch.uint8, device=device)
+            if self.render.max_flow is None:
+                self._rad_max = torch.zeros((b,), **f32)
+            if self.render.backward:
+                self._view_bw = torch.zeros(shape, dtype=torch.uint8, device=device)
+                if self.render.max_flow is None:
+                    self._rad_max_bw = torch.zeros((b,), **f32)
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -436,6 +518,13 @@ class FrameSequence:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
         table = None if tb is None else (tb.pos, tb.ids, tb.age)      # what the three checks cull
         fb = self._check(flow_low, flow_up, matches, valid, table) if self.fb is not None else None
+        view = None
+        if self.render is not None:      # behind the forward-backward check (its occlusion map), on the padded field: reads only
+            occluded = fb.occluded if self.render.occluded is not None else None
+            self._paint(flow_up, left, top, self._view, self._rad_max, occluded)
+            if self.render.backward:      # (fb.flow_bw is the crop of the padded backward field: the view is passed as it is)
+                self._paint(fb.flow_bw, 0, 0, self._view_bw, self._rad_max_bw, None)
+            view = RenderResult(self._view, self._rad_max, self._view_bw)
         flow_up = flow_up[:, :, top:top + h, left:left + w]
         epi = hom = None
         if self._hom is not None:      # behind fb, before epipolar: both see the same candidates unless Homography.cull
@@ -445,7 +534,15 @@ class FrameSequence:
         if self._epi is not None:      # last: its candidates are the rows that are still valid
             hold = hom.planar if hom is not None and self.homography.hold_epipolar else None
             epi = self._epi(matches, valid, h, w, table=table, hold=hold)
-        return FrameResult(flow_low, flow_up, matches, valid, count, tracks, fb, epi, hom)
+        return FrameResult(flow_low, flow_up, matches, valid, count, tracks, fb, epi, hom, view)
+
+    def _paint(self, flow, left, top, image, rad_max, occluded):
+        """ops.flow_to_image with the session's Render into the session's buffers."""
+        b, h, w = self._bhw
+        r = self.render
+        ops.flow_to_image(flow, left, top, h, w, max_flow=r.max_flow, clip_flow=r.clip_flow, order=r.order or self.order, layout=r.layout or self.layout,
+                          occluded=occluded, occluded_color=r.occluded or (0, 0, 0), out=image if rad_max is None else (image, rad_max),
+                          return_max=rad_max is not None)
 
     def _check(self, flow_low, flow_up, matches, valid, table):
         """The forward-backward part of a step, behind the advance / the matches: the backward pair's mask, the backward flow's

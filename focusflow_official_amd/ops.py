@@ -1284,6 +1284,77 @@ def fb_matches(matches: Tensor, valid: Tensor, bw: Tensor, left: int, top: int, 
     return err2, status
 
 
+def flow_to_image(flow: Tensor, left: int = 0, top: int = 0, h: Optional[int] = None, w: Optional[int] = None, max_flow: Optional[float] = None,
+                  clip_flow: Optional[float] = None, order: str = "rgb", layout: str = "hwc", occluded: Optional[Tensor] = None,
+                  occluded_color=(0, 0, 0), out: Optional[Tensor] = None, return_max: bool = False):
+    """A flow field as colours by the Middlebury colour wheel (csrc/flow_viz.hip; the definition is in include/focusflow_hip.h):
+    the reference's flow_viz.flow_to_image on the device, uint8 out.  flow: (B,2,Hp,Wp) fp32, any strides, the padded field whose
+    h x w frame starts at (left, top) (default: everything right of and below (left, top)).  Every sample is scaled by the
+    maximum magnitude of ITS frame, or by max_flow (finite, > 0) where that is given: a fixed scale, beyond which vectors are
+    darkened instead, so that the colours of a video do not pump.  clip_flow (>= 0): np.clip(flow, 0, clip_flow) first, as the
+    reference does it.  order 'rgb' or 'bgr'; layout 'hwc': (B,h,w,3), 'chw': (B,3,h,w).  occluded: None, or a uint8 (B,1,h,w) /
+    (B,h,w) plane, any strides: where it is non-zero the pixel is occluded_color, an (r, g, b) triple of 0 .. 255.  A vector with
+    a non-finite component is left out of the maximum and painted black.  out: a uint8 tensor of the layout's shape, any strides
+    (default: a new contiguous one), or with return_max the tuple (image, rad_max) to write into.  -> the image, or with
+    return_max (image, rad_max (B) fp32: the maxima of the frames, whether or not max_flow replaced them as the scale).  Two
+    launches (one with max_flow and without return_max); enqueues only, so it can be captured."""
+    name = "flow_to_image"
+    b, hp, wp = _fb_field(name, flow, "flow", None, None)
+    dev = flow.device
+    left, top = int(left), int(top)
+    h, w = hp - top if h is None else int(h), wp - left if w is None else int(w)
+    if left < 0 or top < 0 or h < 1 or w < 1 or left + w > wp or top + h > hp:
+        raise _hip.FocusFlowHipError(f"{name}: the {h} x {w} frame at (left, top) = ({left}, {top}) does not lie inside the {hp} x {wp} field")
+    if max_flow is not None and not (float(max_flow) > 0 and math.isfinite(float(max_flow))):
+        raise _hip.FocusFlowHipError(f"{name}: max_flow = {max_flow}: None (the maximum of every frame) or a finite value > 0")
+    if clip_flow is not None and not float(clip_flow) >= 0:
+        raise _hip.FocusFlowHipError(f"{name}: clip_flow = {clip_flow}: None or a value >= 0")
+    if order not in ("rgb", "bgr"):
+        raise _hip.FocusFlowHipError(f"{name}: order = {order!r} ('rgb' or 'bgr')")
+    if layout not in ("hwc", "chw"):
+        raise _hip.FocusFlowHipError(f"{name}: layout = {layout!r} ('hwc' or 'chw')")
+    occ_ld = (0, 0, 0)
+    if occluded is not None:
+        _require_device(occluded, name, "occluded", (torch.uint8,))
+        if occluded.dim() == 4 and occluded.shape[1] == 1:
+            occluded = occluded[:, 0]
+        if tuple(occluded.shape) != (b, h, w) or occluded.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: occluded must be ({b},1,{h},{w}) or ({b},{h},{w}) on {dev}, got {tuple(occluded.shape)} on {occluded.device}")
+        occ_ld = occluded.stride()
+    try:
+        color = tuple(int(c) for c in occluded_color)
+        exact = all(c == x for c, x in zip(color, occluded_color))
+    except (TypeError, ValueError):
+        color, exact = (), False
+    if len(color) != 3 or not exact or not all(0 <= c <= 255 for c in color):
+        raise _hip.FocusFlowHipError(f"{name}: occluded_color = {occluded_color!r}: an (r, g, b) triple of integers 0 .. 255")
+    shape = (b, h, w, 3) if layout == "hwc" else (b, 3, h, w)
+    rad_max = None
+    if isinstance(out, (tuple, list)):      # (image, rad_max): a session's static buffers
+        if not return_max or len(out) != 2:
+            raise _hip.FocusFlowHipError(f"{name}: out must be the image, or with return_max the tuple (image, rad_max)")
+        out, rad_max = out
+        _require_device(rad_max, name, "out (rad_max)", (torch.float32,))
+        if tuple(rad_max.shape) != (b,) or not rad_max.is_contiguous() or rad_max.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: out (rad_max) must be contiguous ({b},) on {dev}, got {tuple(rad_max.shape)} on {rad_max.device}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    else:
+        _require_device(out, name, "out", (torch.uint8,))
+        if tuple(out.shape) != shape or out.device != dev:
+            raise _hip.FocusFlowHipError(f"{name}: out must be {shape} for layout {layout!r} on {dev}, got {tuple(out.shape)} on {out.device}")
+    ld_b, ld_row, ld_col, ld_c = out.stride() if layout == "hwc" else (out.stride(0), out.stride(2), out.stride(3), out.stride(1))
+    clip = -1.0 if clip_flow is None else float(clip_flow)
+    field = (_p(flow), flow.stride(0), flow.stride(1), flow.stride(2), flow.stride(3), b, left, top, h, w, hp, wp)
+    if max_flow is None or return_max:
+        if rad_max is None:
+            rad_max = torch.empty((b,), dtype=torch.float32, device=dev)
+        _hip.call("ff_flow_rad_max", *field, clip, _p(rad_max), _stream())
+    _hip.call("ff_flow_to_image", *field, _p(rad_max if max_flow is None else None), 0.0 if max_flow is None else float(max_flow), clip,
+              _p(occluded), *occ_ld, *color, int(order == "bgr"), _p(out), ld_b, ld_row, ld_col, ld_c, _stream())
+    return (out, rad_max) if return_max else out
+
+
 def epipolar_ws(b: int, n: int, hypotheses: int) -> int:
     """Bytes of workspace ff_epipolar_ransac needs for (B, N, K); 0: the shape is not supported."""
     return _hip.load().ff_epipolar_ws(int(b), int(n), int(hypotheses))

@@ -75,7 +75,9 @@ const char* ff_last_error(void);
  *                shortcut of a stride-2 residual block entry as one launch)
  *   7 (unchanged): entry points only: ff_homography_ws, ff_homography_ransac, ff_homography_residual, ff_epipolar_ransac_hold
  *                (homography check of a video session: a RANSAC homography per pair, a planar / pure-rotation verdict that can
- *                hold the epipolar check back, and the dense residual of the flow against the map) */
+ *                hold the epipolar check back, and the dense residual of the flow against the map)
+ *   7 (unchanged): entry points only: ff_flow_rad_max, ff_flow_to_image (flow images out of a video session: the Middlebury
+ *                colour wheel of the reference's flow_viz.py on the device, uint8 out) */
 #define FF_ABI_VERSION 7
 int ff_abi_version(void);
 
@@ -603,6 +605,49 @@ int ff_homography_ransac(const float* matches, unsigned char* valid, int B, int 
  * pointer, a negative stride. */
 int ff_homography_residual(const float* flow, long long ld_b, long long ld_c, long long ld_row, long long ld_col, const float* Hm,
                            const unsigned char* ok, int B, int Himg, int Wimg, float* out, void* stream);
+/* Flow images (csrc/flow_viz.hip): a flow field as colours, hue for the direction and saturation for the magnitude, by the
+ * Middlebury colour wheel (Baker et al., ICCV 2007).  The definition is the dtype chain of the reference's
+ * core/utils/flow_viz.py::flow_to_image under numpy >= 2 (and of `max_flow`, the extension of the FF-FlowFormer copy of that file);
+ * tests/flow_viz_ref.py restates it in numpy and tests/golden/flow_viz.npz holds the reference's own images.  The field is a padded
+ * (B,2,Hp,Wp) fp32 one given by four element strides, the H x W frame starts at (left, top); (u, v) is its value at a pixel of
+ * the frame, and every operation below is rounded on its own (no FMA), divisions and square roots correctly:
+ *   uc, vc = clip < 0 ? (u, v) : (clamp(u, 0, clip), clamp(v, 0, clip))   fp32  (np.clip(flow, 0, clip): below to 0 as well)
+ *   r      = sqrt(uc uc + vc vc)                                          fp32
+ *   m      = max of r over the sample's frame;  den = m + 1e-5f           fp32  (max_flow given: den = (float)((double) max_flow + 1e-5))
+ *   un, vn = uc / den, vc / den;  rad = sqrt(un un + vn vn)               fp32
+ *   a      = atan2(-vn, -un) / (float) pi                                 fp32  (the angle: atan2 in fp64, rounded once to fp32)
+ *   fk     = ((a + 1) / 2) 54                                             fp32, three roundings
+ *   k0     = floor(fk), clamped to 0 .. 54;  k1 = k0 + 1 == 55 ? 0 : k0 + 1;  f = (double) fk - k0
+ *   per channel c:  col = (1 - f) (wheel[k0][c] / 255.0) + f (wheel[k1][c] / 255.0)                                   fp64
+ *                   col = rad <= 1 ? 1 - (double) rad (1 - col) : col 0.75;  byte = floor(255 col)
+ * wheel: the 55 x 3 table of make_colorwheel (RY 15, YG 6, GC 4, CB 11, BM 13, MR 6).  The angle is the one step with latitude:
+ * an implementation whose atan2 is an ulp off moves 255 col by about 3e-4 and so a byte by one level in fewer than 3e-4 of the
+ * cases.  A zero field is 255 everywhere.  Beyond the reference (np.max gives NaN there and the whole image is garbage): a vector
+ * with a non-finite u or v, or whose r is not finite, is left out of the maximum and painted (0, 0, 0); a frame of such vectors
+ * only has m = 0.
+ *
+ * ff_flow_rad_max: rad_max[b] = m of sample b (B fp32 words, 4-byte aligned).  The call clears the words itself (a memset node
+ * in front of its kernel) and the blocks of a sample meet in an atomic maximum on the bit patterns, which for non-negative floats
+ * is the maximum of the values: exact and independent of the order, and a captured call that is replayed on smaller motion
+ * leaves the smaller maximum.
+ *
+ * ff_flow_to_image: writes the three bytes of every pixel of the frame: dst[b dst_ld_b + y dst_ld_row + x dst_ld_col + c dst_ld_c],
+ * uint8, strides in elements, so one call serves (B,H,W,3), (B,3,H,W) and views of either; swap_rb = 1 writes B,G,R.  rad_max:
+ * the device words of ff_flow_rad_max (called with the same field, geometry and clip), or null and a finite max_flow > 0 (then
+ * vectors beyond it take the 0.75 branch: a fixed scale, so the colours of a video do not pump).  clip < 0: none.  occluded: null,
+ * or a uint8 plane of the frame by three element strides; where it is non-zero the pixel is (occ_r, occ_g, occ_b) instead
+ * (0 .. 255 each, given as R,G,B and written in the destination's order), whatever the vector.  A contiguous, 4-byte aligned
+ * (B,H,W,3) destination is written as whole dwords.
+ *
+ * Both enqueue only (capturable) and allocate nothing.  Refused (FF_EINVAL): a null pointer (but for rad_max with max_flow, and
+ * occluded), B outside 1 .. 65535, H or W < 1, B H W > 2^30, left or top < 0, left + W > Wp, top + H > Hp, a negative stride, a
+ * NaN clip, neither rad_max nor a finite max_flow > 0, swap_rb outside 0 .. 1, a colour outside 0 .. 255. */
+int ff_flow_rad_max(const float* flow, long long ld_b, long long ld_c, long long ld_row, long long ld_col, int B, int left, int top, int H,
+                    int W, int Hp, int Wp, float clip, float* rad_max, void* stream);
+int ff_flow_to_image(const float* flow, long long ld_b, long long ld_c, long long ld_row, long long ld_col, int B, int left, int top, int H,
+                     int W, int Hp, int Wp, const float* rad_max, double max_flow, float clip, const unsigned char* occluded,
+                     long long occ_ld_b, long long occ_ld_row, long long occ_ld_col, int occ_r, int occ_g, int occ_b, int swap_rb,
+                     unsigned char* dst, long long dst_ld_b, long long dst_ld_row, long long dst_ld_col, long long dst_ld_c, void* stream);
 /* coords1 += delta (if delta) ; flow = coords1 - coords0 written to
  * flow4 [npix][4] (zero padded, conv input) and to motion[...,126:128] style
  * slot `slot` ([npix][slot_ld], 2 floats) if non-null.   raft.py:219,223 */
