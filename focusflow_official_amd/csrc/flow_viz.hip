@@ -25,7 +25,7 @@
 #pragma clang fp contract(off)
 #include <climits>
 #include <cmath>
-#include "ff_common.h"
+#include "frame_field.h"
 
 namespace {
 
@@ -33,10 +33,7 @@ constexpr int THREADS = 256;
 constexpr int NCOLS = 55;
 constexpr int MAX_BLOCKS_PER_SAMPLE = 256;      // of the reduction: that many atomics per sample at the most
 
-struct Field {      // a padded (B,2,Hp,Wp) field by element strides, already moved to the frame's corner (left, top)
-    const float* p;
-    long long ld_b, ld_c, ld_row, ld_col;
-};
+using ff::Field;
 
 __device__ __forceinline__ bool finite(float x) { return (__float_as_uint(x) & 0x7fffffffu) < 0x7f800000u; }
 __device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
@@ -192,23 +189,23 @@ __global__ void __launch_bounds__(THREADS) to_image_dense_kernel(Field f, Plane 
 
 }  // namespace
 
-#define FF_REQUIRE_VIZ_FRAME(name)                                                                                                          \
-    FF_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0, name ": B = %d, H = %d, W = %d (all > 0, B <= 65535)", B, H, W);                     \
+// what the two entries ask beyond the frame's place in its field
+#define FF_REQUIRE_VIZ_LIMITS(name)                                                                                                         \
+    FF_REQUIRE(B <= 65535, name ": B = %d (at most 65535: a grid dimension)", B);                                                           \
     FF_REQUIRE((long long)B * H * W <= (1ll << 30), name ": B H W = %d x %d x %d (at most 2^30 pixels)", B, H, W);                          \
-    FF_REQUIRE(left >= 0 && (long long)left + W <= Wp, name ": left = %d with W = %d does not fit Wp = %d", left, W, Wp);                   \
-    FF_REQUIRE(top >= 0 && (long long)top + H <= Hp, name ": top = %d with H = %d does not fit Hp = %d", top, H, Hp);                       \
     FF_REQUIRE(ld_b >= 0 && ld_c >= 0 && ld_row >= 0 && ld_col >= 0, name ": a negative stride of the field");                             \
     FF_REQUIRE(!(clip != clip), name ": clip is a NaN (negative: no clipping)")
 
 extern "C" int ff_flow_rad_max(const float* flow, long long ld_b, long long ld_c, long long ld_row, long long ld_col, int B, int left, int top,
                                int H, int W, int Hp, int Wp, float clip, float* rad_max, void* stream) {
-    FF_REQUIRE_VIZ_FRAME("ff_flow_rad_max");
+    FF_REQUIRE_FRAME_IN_FIELD("ff_flow_rad_max");
+    FF_REQUIRE_VIZ_LIMITS("ff_flow_rad_max");
     FF_REQUIRE(flow && rad_max, "ff_flow_rad_max: null pointer");
     FF_REQUIRE(((size_t)rad_max & 3) == 0, "ff_flow_rad_max: rad_max must be 4-byte aligned");
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const hipError_t e = hipMemsetAsync(rad_max, 0, sizeof(float) * (size_t)B, s);
     if (e != hipSuccess) return ff::fail(FF_EHIP, "ff_flow_rad_max: hipMemsetAsync: %s", hipGetErrorString(e));
-    const Field f = {flow + (long long)top * ld_row + (long long)left * ld_col, ld_b, ld_c, ld_row, ld_col};
+    const Field f = ff::frame_field(flow, ld_b, ld_c, ld_row, ld_col, left, top);
     const long long npix = (long long)H * W;
     // (four pixels per thread before a sample gets a second block: the blocks of a sample meet in an atomic)
     const unsigned blocks = (unsigned)std::min<long long>((npix + 4 * THREADS - 1) / (4 * THREADS), MAX_BLOCKS_PER_SAMPLE);
@@ -221,7 +218,8 @@ extern "C" int ff_flow_to_image(const float* flow, long long ld_b, long long ld_
                                 long long occ_ld_b, long long occ_ld_row, long long occ_ld_col, int occ_r, int occ_g, int occ_b, int swap_rb,
                                 unsigned char* dst, long long dst_ld_b, long long dst_ld_row, long long dst_ld_col, long long dst_ld_c,
                                 void* stream) {
-    FF_REQUIRE_VIZ_FRAME("ff_flow_to_image");
+    FF_REQUIRE_FRAME_IN_FIELD("ff_flow_to_image");
+    FF_REQUIRE_VIZ_LIMITS("ff_flow_to_image");
     FF_REQUIRE(flow && dst, "ff_flow_to_image: null pointer (flow or dst)");
     FF_REQUIRE(rad_max || (max_flow > 0.0 && std::isfinite(max_flow)),
                "ff_flow_to_image: max_flow = %g without rad_max (a device maximum, or a finite max_flow > 0)", max_flow);
@@ -231,7 +229,7 @@ extern "C" int ff_flow_to_image(const float* flow, long long ld_b, long long ld_
     FF_REQUIRE(occ_ld_b >= 0 && occ_ld_row >= 0 && occ_ld_col >= 0, "ff_flow_to_image: a negative stride of the occlusion plane");
     FF_REQUIRE(dst_ld_b >= 0 && dst_ld_row >= 0 && dst_ld_col >= 0 && dst_ld_c >= 0, "ff_flow_to_image: a negative stride of the destination");
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const Field f = {flow + (long long)top * ld_row + (long long)left * ld_col, ld_b, ld_c, ld_row, ld_col};
+    const Field f = ff::frame_field(flow, ld_b, ld_c, ld_row, ld_col, left, top);
     const Plane occ = {occluded, occ_ld_b, occ_ld_row, occ_ld_col};
     const float den_fixed = rad_max ? 0.f : (float)(max_flow + 1e-5);
     const unsigned paint = swap_rb ? (unsigned)occ_b | (unsigned)occ_g << 8 | (unsigned)occ_r << 16

@@ -10,7 +10,7 @@
 // Every output element is written by exactly one thread from values it loads itself: no atomics, no LDS, no ordering
 // between threads.  One launch each on the caller's stream, no allocation, no synchronisation.
 #include <climits>
-#include "ff_common.h"
+#include "frame_field.h"
 
 namespace {
 
@@ -40,8 +40,7 @@ __global__ void __launch_bounds__(THREADS) pad_convert_kernel(const T* __restric
 
 // one thread per (b, n) row
 __global__ void __launch_bounds__(THREADS) matches_kernel(const int* __restrict__ points, const int* __restrict__ count, int N,
-                                                          const float* __restrict__ flow, long long fb, long long fc, long long fy, long long fx,
-                                                          int left, int top, int H, int W, float4* __restrict__ matches,
+                                                          ff::Field flow, int H, int W, float4* __restrict__ matches,
                                                           unsigned char* __restrict__ valid, int rows) {
     const int r = blockIdx.x * THREADS + threadIdx.x;
     if (r >= rows) return;
@@ -51,8 +50,8 @@ __global__ void __launch_bounds__(THREADS) matches_kernel(const int* __restrict_
     const int x = points[2 * (long long)r], y = points[2 * (long long)r + 1];
     // (a row of the count whose point lies outside the frame is not the detector's: it is written as an empty row, never read through)
     if (n < count[b] && x >= 0 && x < W && y >= 0 && y < H) {
-        const float* f = flow + b * fb + (long long)(y + top) * fy + (long long)(x + left) * fx;
-        const float u = f[0], v = f[fc];
+        const float* f = flow.p + b * flow.ld_b + (long long)y * flow.ld_row + (long long)x * flow.ld_col;
+        const float u = f[0], v = f[flow.ld_c];
         const float tx = (float)x + u, ty = (float)y + v;
         m = make_float4((float)x, (float)y, tx, ty);
         ok = tx >= 0.f && tx <= (float)(W - 1) && ty >= 0.f && ty <= (float)(H - 1);      // (NaN: 0)
@@ -74,16 +73,11 @@ int launch_pad(const char* what, const T* src, long long sb, long long sy, long 
 
 }  // namespace
 
-#define FF_REQUIRE_PAD_GEOMETRY(name)                                                                                                      \
-    FF_REQUIRE(B > 0 && H > 0 && W > 0, name ": B = %d, H = %d, W = %d (all > 0)", B, H, W);                                                \
-    FF_REQUIRE(left >= 0 && (long long)left + W <= Wp, name ": left = %d with W = %d does not fit Wp = %d", left, W, Wp);                   \
-    FF_REQUIRE(top >= 0 && (long long)top + H <= Hp, name ": top = %d with H = %d does not fit Hp = %d", top, H, Hp);                       \
-    FF_REQUIRE((long long)Hp * Wp <= INT_MAX / 4, name ": Hp x Wp = %d x %d is too large a plane", Hp, Wp)
-
 extern "C" int ff_frame_ingest(const unsigned char* src, long long ld_b, long long ld_row, long long ld_col, long long ld_c, int swap_rb, int B,
                                int H, int W, int left, int top, int Hp, int Wp, float* dst, void* stream) {
     FF_REQUIRE(src && dst, "ff_frame_ingest: null pointer (src or dst)");
-    FF_REQUIRE_PAD_GEOMETRY("ff_frame_ingest");
+    FF_REQUIRE_FRAME_IN_FIELD("ff_frame_ingest");
+    FF_REQUIRE((long long)Hp * Wp <= INT_MAX / 4, "ff_frame_ingest: Hp x Wp = %d x %d is too large a plane", Hp, Wp);
     FF_REQUIRE(swap_rb == 0 || swap_rb == 1, "ff_frame_ingest: swap_rb = %d (0 = R,G,B source, 1 = B,G,R source)", swap_rb);
     return launch_pad("ff_frame_ingest", src, ld_b, ld_row, ld_col, ld_c, 3, swap_rb, B, H, W, left, top, Hp, Wp, dst, stream);
 }
@@ -91,7 +85,8 @@ extern "C" int ff_frame_ingest(const unsigned char* src, long long ld_b, long lo
 extern "C" int ff_pad_replicate(const void* src, int src_is_u8, long long ld_b, long long ld_row, long long ld_col, int B, int H, int W, int left,
                                 int top, int Hp, int Wp, float* dst, void* stream) {
     FF_REQUIRE(src && dst, "ff_pad_replicate: null pointer (src or dst)");
-    FF_REQUIRE_PAD_GEOMETRY("ff_pad_replicate");
+    FF_REQUIRE_FRAME_IN_FIELD("ff_pad_replicate");
+    FF_REQUIRE((long long)Hp * Wp <= INT_MAX / 4, "ff_pad_replicate: Hp x Wp = %d x %d is too large a plane", Hp, Wp);
     FF_REQUIRE(src_is_u8 == 0 || src_is_u8 == 1, "ff_pad_replicate: src_is_u8 = %d (0 = fp32 source, 1 = uint8 source)", src_is_u8);
     if (src_is_u8)
         return launch_pad("ff_pad_replicate", static_cast<const unsigned char*>(src), ld_b, ld_row, ld_col, 0, 1, 0, B, H, W, left, top, Hp, Wp, dst,
@@ -105,12 +100,10 @@ extern "C" int ff_keypoint_matches(const int* points, const int* count, int N, c
                                    void* stream) {
     FF_REQUIRE(points && count && flow_up && matches && valid, "ff_keypoint_matches: null pointer");
     FF_REQUIRE(B > 0 && N > 0 && (long long)B * N <= INT_MAX / 4, "ff_keypoint_matches: B = %d, N = %d (both > 0, B N < 2^29)", B, N);
-    FF_REQUIRE(H > 0 && W > 0, "ff_keypoint_matches: H = %d, W = %d (both > 0)", H, W);
-    FF_REQUIRE(left >= 0 && (long long)left + W <= Wp, "ff_keypoint_matches: left = %d with W = %d does not fit Wp = %d", left, W, Wp);
-    FF_REQUIRE(top >= 0 && (long long)top + H <= Hp, "ff_keypoint_matches: top = %d with H = %d does not fit Hp = %d", top, H, Hp);
+    FF_REQUIRE_FRAME_IN_FIELD("ff_keypoint_matches");
     FF_REQUIRE(((size_t)matches & 15) == 0, "ff_keypoint_matches: matches must be 16-byte aligned");
     const int rows = B * N;
     matches_kernel<<<(rows + THREADS - 1) / THREADS, THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-        points, count, N, flow_up, ld_b, ld_c, ld_row, ld_col, left, top, H, W, reinterpret_cast<float4*>(matches), valid, rows);
+        points, count, N, ff::frame_field(flow_up, ld_b, ld_c, ld_row, ld_col, left, top), H, W, reinterpret_cast<float4*>(matches), valid, rows);
     return ff::check_launch("ff_keypoint_matches");
 }

@@ -14,7 +14,7 @@
 // synchronisation; every launch goes to the caller's stream.
 #pragma clang fp contract(off)
 #include <climits>
-#include "ff_common.h"
+#include "frame_field.h"
 
 namespace {
 
@@ -169,8 +169,7 @@ __global__ void __launch_bounds__(THREADS) mask_scatter_kernel(const float2* __r
 
 // one thread per (b, slot)
 __global__ void __launch_bounds__(THREADS) advance_kernel(float2* __restrict__ pos, long long* __restrict__ ids, int* __restrict__ age, int N,
-                                                          const float* __restrict__ flow, long long fb, long long fc, long long fy_, long long fx_,
-                                                          int left, int top, int H, int W, float4* __restrict__ matches,
+                                                          ff::Field flow, int H, int W, float4* __restrict__ matches,
                                                           unsigned char* __restrict__ valid, long long* __restrict__ ids_out,
                                                           int* __restrict__ age_out, int rows) {
     const int r = blockIdx.x * THREADS + threadIdx.x;
@@ -181,15 +180,8 @@ __global__ void __launch_bounds__(THREADS) advance_kernel(float2* __restrict__ p
     unsigned char ok = 0;
     if (id >= 0) {
         const float2 p = pos[r];
-        // (the invariant of a live slot puts x0, y0 inside the frame; the clamps hold the taps there whatever the table holds)
-        const int x0 = (int)fminf(fmaxf(floorf(p.x), 0.f), (float)(W - 1)), y0 = (int)fminf(fmaxf(floorf(p.y), 0.f), (float)(H - 1));
-        const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-        const float fx = __fsub_rn(p.x, (float)x0), fy = __fsub_rn(p.y, (float)y0);
-        const float* f = flow + (r / N) * fb;
-        const long long o00 = (long long)(y0 + top) * fy_ + (long long)(x0 + left) * fx_, o01 = (long long)(y0 + top) * fy_ + (long long)(x1 + left) * fx_;
-        const long long o10 = (long long)(y1 + top) * fy_ + (long long)(x0 + left) * fx_, o11 = (long long)(y1 + top) * fy_ + (long long)(x1 + left) * fx_;
-        const float u = ff::blend(f[o00], f[o01], f[o10], f[o11], fx, fy);
-        const float v = ff::blend(f[fc + o00], f[fc + o01], f[fc + o10], f[fc + o11], fx, fy);
+        float u, v;      // (the invariant of a live slot puts the position inside the frame; the read holds its taps there whatever the table holds)
+        ff::bilinear_uv(flow, r / N, p.x, p.y, H, W, u, v);
         const float tx = __fadd_rn(p.x, u), ty = __fadd_rn(p.y, v);
         m = make_float4(p.x, p.y, tx, ty);
         ok = tx >= 0.f && tx <= (float)(W - 1) && ty >= 0.f && ty <= (float)(H - 1);      // (NaN: 0)
@@ -205,6 +197,7 @@ __global__ void __launch_bounds__(THREADS) advance_kernel(float2* __restrict__ p
 
 }  // namespace
 
+// (ff_tracks_advance has a field as well: FF_REQUIRE_FRAME_IN_FIELD says the first line again there, which costs nothing)
 #define FF_REQUIRE_TRACK_FRAME(name)                                                                                              \
     FF_REQUIRE(N >= 1 && N <= MAX_SLOTS, name ": N = %d (1 .. %d slots)", N, MAX_SLOTS);                                          \
     FF_REQUIRE(B > 0 && H > 0 && W > 0, name ": B = %d, H = %d, W = %d (all > 0)", B, H, W);                                      \
@@ -242,12 +235,11 @@ extern "C" int ff_tracks_advance(float* pos, long long* ids, int* age, int N, co
                                  unsigned char* valid, long long* ids_out, int* age_out, void* stream) {
     FF_REQUIRE(pos && ids && age && flow_up && matches && valid && ids_out && age_out, "ff_tracks_advance: null pointer");
     FF_REQUIRE_TRACK_FRAME("ff_tracks_advance");
-    FF_REQUIRE(left >= 0 && (long long)left + W <= Wp, "ff_tracks_advance: left = %d with W = %d does not fit Wp = %d", left, W, Wp);
-    FF_REQUIRE(top >= 0 && (long long)top + H <= Hp, "ff_tracks_advance: top = %d with H = %d does not fit Hp = %d", top, H, Hp);
+    FF_REQUIRE_FRAME_IN_FIELD("ff_tracks_advance");
     FF_REQUIRE(((size_t)pos & 7) == 0 && ((size_t)matches & 15) == 0, "ff_tracks_advance: pos must be 8-byte aligned, matches 16-byte aligned");
     const int rows = B * N;
     advance_kernel<<<(rows + THREADS - 1) / THREADS, THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-        reinterpret_cast<float2*>(pos), ids, age, N, flow_up, ld_b, ld_c, ld_row, ld_col, left, top, H, W, reinterpret_cast<float4*>(matches), valid,
-        ids_out, age_out, rows);
+        reinterpret_cast<float2*>(pos), ids, age, N, ff::frame_field(flow_up, ld_b, ld_c, ld_row, ld_col, left, top), H, W,
+        reinterpret_cast<float4*>(matches), valid, ids_out, age_out, rows);
     return ff::check_launch("ff_tracks_advance");
 }

@@ -70,7 +70,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import ops
-from .geometry import EpiResult, EpipolarCheck, HomResult, HomographyCheck, as_epipolar, as_homography
+from .geometry import EpiResult, EpipolarCheck, HomResult, HomographyCheck, as_config, as_epipolar, as_homography
+from .graph import CapturedStep
 from .model import FF_RAFT_FUSION
 from .tracks import MAX_SLOTS, TrackResult, TrackTable
 
@@ -85,20 +86,18 @@ class FBCheck(NamedTuple):
     iters: Optional[int] = None
     warm: bool = True
 
+    def validated(self):
+        """-> self, or a ValueError that names `fb` and the field."""
+        if not (self.alpha >= 0 and self.beta >= 0):
+            raise ValueError(f"fb: alpha={self.alpha}, beta={self.beta}: both >= 0 (and no NaN)")
+        if self.iters is not None and int(self.iters) < 1:
+            raise ValueError(f"fb: iters={self.iters}: None (the session's raft_iters) or at least 1")
+        return self
+
 
 def as_fb(fb) -> Optional[FBCheck]:
     """None / False -> None, True -> the defaults, an FBCheck -> itself, checked; anything else is a ValueError."""
-    if fb is None or fb is False:
-        return None
-    if fb is True:
-        return FBCheck()
-    if not isinstance(fb, FBCheck):
-        raise ValueError(f"fb: True or a frames.FBCheck(alpha, beta, iters, warm) expected, got {type(fb).__name__}")
-    if not (fb.alpha >= 0 and fb.beta >= 0):
-        raise ValueError(f"fb: alpha={fb.alpha}, beta={fb.beta}: both >= 0 (and no NaN)")
-    if fb.iters is not None and int(fb.iters) < 1:
-        raise ValueError(f"fb: iters={fb.iters}: None (the session's raft_iters) or at least 1")
-    return fb
+    return as_config("fb", fb, FBCheck)
 
 
 class FBResult(NamedTuple):
@@ -125,28 +124,26 @@ class Render(NamedTuple):
     occluded: Optional[tuple] = None
     backward: bool = False
 
+    def validated(self):
+        """-> self, or a ValueError that names `render` and the field."""
+        if self.max_flow is not None and not (self.max_flow > 0 and self.max_flow != float("inf")):
+            raise ValueError(f"render: max_flow={self.max_flow}: None (every frame's own maximum) or a finite value > 0")
+        if self.clip_flow is not None and not self.clip_flow >= 0:
+            raise ValueError(f"render: clip_flow={self.clip_flow}: None or a value >= 0")
+        if self.order not in (None, "rgb", "bgr"):
+            raise ValueError(f"render: order={self.order!r}: None (the session's), 'rgb' or 'bgr'")
+        if self.layout not in (None, "hwc", "chw"):
+            raise ValueError(f"render: layout={self.layout!r}: None (the session's), 'hwc' or 'chw'")
+        c = self.occluded
+        if c is not None and (not isinstance(c, (tuple, list)) or len(c) != 3
+                              or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x <= 255 for x in c)):
+            raise ValueError(f"render: occluded={c!r}: None or an (r, g, b) triple of integers 0 .. 255")
+        return self
+
 
 def as_render(render) -> Optional[Render]:
     """None / False -> None, True -> the defaults, a Render -> itself, checked; anything else is a ValueError."""
-    if render is None or render is False:
-        return None
-    if render is True:
-        return Render()
-    if not isinstance(render, Render):
-        raise ValueError(f"render: True or a frames.Render(max_flow, clip_flow, order, layout, occluded, backward) expected, got {type(render).__name__}")
-    if render.max_flow is not None and not (render.max_flow > 0 and render.max_flow != float("inf")):
-        raise ValueError(f"render: max_flow={render.max_flow}: None (every frame's own maximum) or a finite value > 0")
-    if render.clip_flow is not None and not render.clip_flow >= 0:
-        raise ValueError(f"render: clip_flow={render.clip_flow}: None or a value >= 0")
-    if render.order not in (None, "rgb", "bgr"):
-        raise ValueError(f"render: order={render.order!r}: None (the session's), 'rgb' or 'bgr'")
-    if render.layout not in (None, "hwc", "chw"):
-        raise ValueError(f"render: layout={render.layout!r}: None (the session's), 'hwc' or 'chw'")
-    if render.occluded is not None:
-        c = render.occluded
-        if not isinstance(c, (tuple, list)) or len(c) != 3 or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x <= 255 for x in c):
-            raise ValueError(f"render: occluded={c!r}: None or an (r, g, b) triple of integers 0 .. 255")
-    return render
+    return as_config("render", render, Render)
 
 
 class RenderResult(NamedTuple):
@@ -246,6 +243,90 @@ for _n in range(1, 2 ** len(_OPTIONAL)):      # (`hom` and `view` are the highes
 del _n, _rows, _cls
 
 
+class ForwardBackward:
+    """The forward-backward part of a session's step with the buffers it keeps: the backward pair's mask (unpadded and padded;
+    None where the session's own mask serves) and the backward flow's start (None without FBCheck.warm).  Enqueues only."""
+
+    def __init__(self, config: FBCheck):
+        self.config = config
+        self.mask_det = self.mask = self.init = None
+
+    def prepare(self, b, h, w, hp, wp, device, own_mask):
+        """The buffers for a (B,h,w) frame in an hp x wp field; own_mask: the session detects, so the backward pair needs a mask."""
+        f32 = dict(dtype=torch.float32, device=device)
+        if own_mask:      # (with caller-supplied masks the backward mask is the session's _mask_next)
+            self.mask_det, self.mask = torch.zeros((b, 1, h, w), **f32), torch.zeros((b, 1, hp, wp), **f32)
+        if self.config.warm:
+            self.init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
+            ops.negate(self.init, self.init)      # (makes the constant negate() reads now, not inside a capture)
+
+    def reset(self):
+        if self.init is not None:
+            self.init.zero_()
+
+    def __call__(self, seq, flow_low, flow_up, matches, valid, table) -> FBResult:
+        """Behind the advance / the matches of session `seq`: the backward pair's mask, the backward flow's start, the backward
+        flow, the dense check, the point check (which clears `valid` and culls the table)."""
+        b, h, w = seq._bhw
+        left, top, hp, wp = seq._pad
+        fb, det, tb = self.config, seq.keypoints, seq._table
+        mask = None
+        if seq._reads_mask:
+            if det is None:
+                mask = seq._mask_next
+            else:
+                if tb is not None:      # the table as the advance left it, before any culling: the tracks in the newest frame
+                    ops.tracks_mask(tb.pos, tb.ids, h, w, out=self.mask_det)
+                else:
+                    inner = seq._img2[:, :, top:top + h, left:left + w]
+                    ops.good_features(inner, det.max_corners, det.quality_level, det.min_distance, out=self.mask_det, ws=det._workspace(inner))
+                mask = ops.pad_replicate(self.mask_det, seq.pad_mode, out=self.mask)
+        kw = {}
+        if fb.warm:
+            if seq.warm_start:      # (flow_init holds forward_interpolate(flow_low) already)
+                ops.negate(seq._flow_init, self.init)
+            else:
+                ops.negate(ops.forward_interpolate(flow_low, out=self.init), self.init)
+            kw = dict(flow_init=self.init)
+        with seq._captured.guard(1):      # a captured forward zeroes and fills the capture's guard words: the backward one gets a pair of its own
+            _, flow_bw = seq.model(seq._img2, seq._img1, mask, None, raft_iters=seq.iters if fb.iters is None else int(fb.iters), test_mode=True, **kw)
+        err2, occluded = ops.fb_dense(flow_up, flow_bw, left, top, h, w, fb.alpha, fb.beta)
+        point_err2 = status = None
+        if matches is not None:
+            point_err2, status = ops.fb_matches(matches, valid, flow_bw, left, top, h, w, fb.alpha, fb.beta, table=table)
+        return FBResult(flow_bw[:, :, top:top + h, left:left + w], err2, occluded, point_err2, status)
+
+
+class FlowRenderer:
+    """ops.flow_to_image with a session's Render into the buffers it keeps: the image and the maximum it was scaled by (None with
+    Render.max_flow), and with Render.backward the same for the backward flow.  order, layout: the session's.  Enqueues only."""
+
+    def __init__(self, config: Render, order, layout):
+        self.config, self.order, self.layout = config, config.order or order, config.layout or layout
+        self.image = self.rad_max = self.image_bw = self.rad_max_bw = None
+
+    def prepare(self, b, h, w, device):
+        def pair():
+            image = torch.zeros((b, h, w, 3) if self.layout == "hwc" else (b, 3, h, w), dtype=torch.uint8, device=device)
+            return image, torch.zeros((b,), dtype=torch.float32, device=device) if self.config.max_flow is None else None
+        self.image, self.rad_max = pair()
+        if self.config.backward:
+            self.image_bw, self.rad_max_bw = pair()
+
+    def _paint(self, flow, left, top, h, w, image, rad_max, occluded):
+        r = self.config
+        ops.flow_to_image(flow, left, top, h, w, max_flow=r.max_flow, clip_flow=r.clip_flow, order=self.order, layout=self.layout,
+                          occluded=occluded, occluded_color=r.occluded or (0, 0, 0), out=image if rad_max is None else (image, rad_max),
+                          return_max=rad_max is not None)
+
+    def __call__(self, flow_up, left, top, h, w, fb: Optional[FBResult]) -> RenderResult:
+        """Behind the forward-backward check (its occlusion map), on the padded field flow_up: reads only."""
+        self._paint(flow_up, left, top, h, w, self.image, self.rad_max, fb.occluded if self.config.occluded is not None else None)
+        if self.config.backward:      # (fb.flow_bw is the crop of the padded backward field: the view is passed as it is)
+            self._paint(fb.flow_bw, 0, 0, h, w, self.image_bw, self.rad_max_bw, None)
+        return RenderResult(self.image, self.rad_max, self.image_bw)
+
+
 class FrameSequence:
     """`model(image1, image2, mask1, None, raft_iters, flow_init, test_mode=True)` over the consecutive frames of a video.
 
@@ -259,9 +340,10 @@ class FrameSequence:
     A step is: copy, ingest, detect, pad the mask, the model forward, forward_interpolate into the flow_init buffer
     (warm_start=True), matches.  graph=True: one hipGraph replay; the first frame after construction, reset() or a change
     of (B,H,W), mask dtype or device is only ingested, the graph is captured on the push after it, and such a change also
-    starts a new sequence.  The range guard works as in graph.GraphedForward: static guard words, ops.guard_check before a
-    replay, ops.guard_queue behind it.  graph=False: the same operations issued one by one.  push() adds no host
-    synchronisation of its own (a capture waits for the device, as every capture does).
+    starts a new sequence.  Capture, replay and the range guard around them are graph.CapturedStep's, as for
+    graph.GraphedForward: static guard words, ops.guard_check before a replay, ops.guard_queue behind it.  graph=False: the
+    same operations issued one by one.  push() adds no host synchronisation of its own (a capture waits for the device, as
+    every capture does).
 
     keypoints=det (keypoints.GoodFeatures): det runs on the unpadded interior of image1, as the reference makes its masks
     from the original image; the mask is then replicate-padded as evaluate.evaluate_loader pads masks, mask1 =
@@ -356,13 +438,13 @@ class FrameSequence:
             raise ValueError("model: FrameSequence runs the eval-mode forward: call model.eval() first")
 
     def _drop(self):
-        self._cuda_graph = self._result = self._guard_words = None      # (the old graph's buffers go before the new ones come)
+        self._captured = None      # the graph.CapturedStep of `_step`; (the old graph's buffers go before the new ones come)
         self._u8 = self._mask_in = self._img1 = self._img2 = self._mask1 = self._mask_next = self._mask_det = self._flow_init = None
         self._table = None
-        self._fb_mask = self._fb_mask_det = self._fb_init = self._guard_words_bw = None
+        self._fb = None      # the ForwardBackward: the backward pair's mask and the backward flow's start
         self._epi = None      # the geometry.EpipolarCheck: workspace, outputs, the epoch word
         self._hom = self._hom_valid = None      # the geometry.HomographyCheck: the same, and the dense residual; the copy of `valid` it judges without cull
-        self._view = self._view_bw = self._rad_max = self._rad_max_bw = None      # the flow images and the maxima they were scaled by
+        self._painter = None      # the FlowRenderer: the flow images and the maxima they were scaled by
         self._frames = 0      # frames of the running sequence that have been ingested
 
     @property
@@ -389,7 +471,12 @@ class FrameSequence:
         fb=, before the first pair and for plain RAFT."""
         if self.fb is None or not self._reads_mask or self._frames < 2:
             return None
-        return self._fb_mask if self._fb_mask is not None else self._mask_next      # (caller-supplied: the mask that came with this frame)
+        return self._fb.mask if self._fb.mask is not None else self._mask_next      # (caller-supplied: the mask that came with this frame)
+
+    @property
+    def _fb_init(self):
+        """What the backward flow starts from (FBCheck.warm); None without."""
+        return self._fb.init if self._fb is not None else None
 
     def reset(self):
         """A sequence boundary: the next push returns None and the pair after it starts cold, with an empty track table (ids
@@ -397,8 +484,8 @@ class FrameSequence:
         self._frames = 0
         if self._flow_init is not None:
             self._flow_init.zero_()
-        if self._fb_init is not None:
-            self._fb_init.zero_()
+        if self._fb is not None:
+            self._fb.reset()
         if self._table is not None:
             self._table.reset()
 
@@ -458,11 +545,8 @@ class FrameSequence:
         if self._slots:
             self._table = TrackTable(b, self._slots, device)
         if self.fb is not None:
-            if self._reads_mask and self.keypoints is not None:      # (with caller-supplied masks the backward mask is _mask_next)
-                self._fb_mask_det, self._fb_mask = torch.zeros((b, 1, h, w), **f32), torch.zeros((b, 1, hp, wp), **f32)
-            if self.fb.warm:
-                self._fb_init = torch.zeros((b, 2, hp // 8, wp // 8), **f32)
-                ops.negate(self._fb_init, self._fb_init)      # (makes the constant negate() reads now, not inside a capture)
+            self._fb = ForwardBackward(self.fb)
+            self._fb.prepare(b, h, w, hp, wp, device, own_mask=self._reads_mask and self.keypoints is not None)
         rows = self._slots or (self.keypoints.max_corners if self.keypoints is not None else 0)      # N of the matches the checks judge
         if self.epipolar is not None:
             self._epi = EpipolarCheck(self.epipolar)
@@ -473,14 +557,10 @@ class FrameSequence:
             if not self.homography.cull:
                 self._hom_valid = torch.zeros((b, rows), dtype=torch.uint8, device=device)
         if self.render is not None:
-            shape = (b, h, w, 3) if (self.render.layout or self.layout) == "hwc" else (b, 3, h, w)
-            self._view = torch.zeros(shape, dtype=torch.uint8, device=device)
-            if self.render.max_flow is None:
-                self._rad_max = torch.zeros((b,), **f32)
-            if self.render.backward:
-                self._view_bw = torch.zeros(shape, dtype=torch.uint8, device=device)
-                if self.render.max_flow is None:
-                    self._rad_max_bw = torch.zeros((b,), **f32)
+            self._painter = FlowRenderer(self.render, self.order, self.layout)
+            self._painter.prepare(b, h, w, device)
+        labels = ("FrameSequence replay",) + ("FrameSequence replay (the backward flow)",) * (self.fb is not None)
+        self._captured = CapturedStep(device, labels, getattr(self.model, "flow_net", None))
 
     def _ingest(self):
         """The uploaded frame (and mask) -> image2 (and the mask that goes with it)."""
@@ -517,14 +597,8 @@ class FrameSequence:
         elif det is not None:
             matches, valid = ops.keypoint_matches(points, count, flow_up, left, top, h, w)
         table = None if tb is None else (tb.pos, tb.ids, tb.age)      # what the three checks cull
-        fb = self._check(flow_low, flow_up, matches, valid, table) if self.fb is not None else None
-        view = None
-        if self.render is not None:      # behind the forward-backward check (its occlusion map), on the padded field: reads only
-            occluded = fb.occluded if self.render.occluded is not None else None
-            self._paint(flow_up, left, top, self._view, self._rad_max, occluded)
-            if self.render.backward:      # (fb.flow_bw is the crop of the padded backward field: the view is passed as it is)
-                self._paint(fb.flow_bw, 0, 0, self._view_bw, self._rad_max_bw, None)
-            view = RenderResult(self._view, self._rad_max, self._view_bw)
+        fb = self._fb(self, flow_low, flow_up, matches, valid, table) if self._fb is not None else None
+        view = self._painter(flow_up, left, top, h, w, fb) if self._painter is not None else None      # behind fb: its occlusion map
         flow_up = flow_up[:, :, top:top + h, left:left + w]
         epi = hom = None
         if self._hom is not None:      # behind fb, before epipolar: both see the same candidates unless Homography.cull
@@ -536,82 +610,19 @@ class FrameSequence:
             epi = self._epi(matches, valid, h, w, table=table, hold=hold)
         return FrameResult(flow_low, flow_up, matches, valid, count, tracks, fb, epi, hom, view)
 
-    def _paint(self, flow, left, top, image, rad_max, occluded):
-        """ops.flow_to_image with the session's Render into the session's buffers."""
-        b, h, w = self._bhw
-        r = self.render
-        ops.flow_to_image(flow, left, top, h, w, max_flow=r.max_flow, clip_flow=r.clip_flow, order=r.order or self.order, layout=r.layout or self.layout,
-                          occluded=occluded, occluded_color=r.occluded or (0, 0, 0), out=image if rad_max is None else (image, rad_max),
-                          return_max=rad_max is not None)
-
-    def _check(self, flow_low, flow_up, matches, valid, table):
-        """The forward-backward part of a step, behind the advance / the matches: the backward pair's mask, the backward flow's
-        start, the backward flow, the dense check, the point check (which clears `valid` and culls the table).  -> FBResult."""
-        b, h, w = self._bhw
-        left, top, hp, wp = self._pad
-        fb, det, tb = self.fb, self.keypoints, self._table
-        mask = None
-        if self._reads_mask:
-            if det is None:
-                mask = self._mask_next
-            else:
-                if tb is not None:      # the table as the advance left it, before any culling: the tracks in the newest frame
-                    ops.tracks_mask(tb.pos, tb.ids, h, w, out=self._fb_mask_det)
-                else:
-                    inner = self._img2[:, :, top:top + h, left:left + w]
-                    ops.good_features(inner, det.max_corners, det.quality_level, det.min_distance, out=self._fb_mask_det, ws=det._workspace(inner))
-                mask = ops.pad_replicate(self._fb_mask_det, self.pad_mode, out=self._fb_mask)
-        kw = {}
-        if fb.warm:
-            if self.warm_start:      # (flow_init holds forward_interpolate(flow_low) already)
-                ops.negate(self._flow_init, self._fb_init)
-            else:
-                ops.negate(ops.forward_interpolate(flow_low, out=self._fb_init), self._fb_init)
-            kw = dict(flow_init=self._fb_init)
-        # a captured forward zeroes and fills the capture's guard words: the backward one gets a pair of its own
-        st = ops._guard_state()
-        words = st["capture_words"]
-        if words is not None and self._guard_words_bw is not None:
-            st["capture_words"] = self._guard_words_bw
-        try:
-            _, flow_bw = self.model(self._img2, self._img1, mask, None, raft_iters=self.iters if fb.iters is None else int(fb.iters), test_mode=True, **kw)
-        finally:
-            st["capture_words"] = words
-        err2, occluded = ops.fb_dense(flow_up, flow_bw, left, top, h, w, fb.alpha, fb.beta)
-        point_err2 = status = None
-        if matches is not None:
-            point_err2, status = ops.fb_matches(matches, valid, flow_bw, left, top, h, w, fb.alpha, fb.beta, table=table)
-        return FBResult(flow_bw[:, :, top:top + h, left:left + w], err2, occluded, point_err2, status)
-
-    def _capture(self, warmup=3):
-        """graph.GraphedForward's capture around `_step`: warm-up steps on a side stream (they pack weights, set kernel
-        attributes, decide the routes and warm the allocator), what they changed put back, then the capture with static
-        guard words."""
+    def _saved(self):
+        """What the warm-up steps of a capture change, saved now: -> the callable that puts it back."""
         # (the warm-up steps would spend epochs: graph and eager draw alike)
         epochs = [c.epoch for c in (self._epi, self._hom) if c is not None]
         keep = [(t, t.clone()) for t in (self._img1, self._img2, self._mask1, self._mask_next, self._flow_init, *epochs) if t is not None]
         table = self._table.state() if self._table is not None else None      # (the warm-up steps would move tracks and spend ids)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._step()
+
+        def put_back():
             for t, saved in keep:
                 t.copy_(saved)
             if table is not None:
                 self._table.load_state(table)
-        torch.cuda.current_stream().wait_stream(side)
-        ops.guard_check(sync=True)
-        self._guard_words = torch.zeros(2, dtype=torch.int32, device=self._img1.device) if ops.RANGE_GUARD else None
-        self._guard_words_bw = torch.zeros(2, dtype=torch.int32, device=self._img1.device) if ops.RANGE_GUARD and self.fb is not None else None
-        st = ops._guard_state()
-        st["capture_words"] = self._guard_words
-        self._cuda_graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(self._cuda_graph):
-                self._result = self._step()
-        finally:
-            st["capture_words"] = None
+        return put_back
 
     def push(self, frame, mask=None):
         """The next frame of the video (and, for FF-RAFT without a detector, its unpadded key-point mask).  -> None for the
@@ -638,12 +649,6 @@ class FrameSequence:
                 return None
             if not self.graph:
                 return self._step()
-            if self._cuda_graph is None:
-                self._capture()
-            ops.guard_check()                   # (raises if an earlier replay left the split formats' range)
-            self._cuda_graph.replay()
-            if self._guard_words is not None:
-                ops.guard_queue(self._guard_words, "FrameSequence replay", getattr(self.model, "flow_net", None))
-            if self._guard_words_bw is not None:
-                ops.guard_queue(self._guard_words_bw, "FrameSequence replay (the backward flow)", getattr(self.model, "flow_net", None))
-            return self._result
+            if self._captured.graph is None:
+                self._captured.capture(self._step, self._saved())
+            return self._captured.replay()

@@ -64,14 +64,16 @@ def _permille(ratio):
     return int(round(1000 * ratio))
 
 
-def _as_config(value, cls):
-    """None / False -> None, True -> the defaults, a `cls` -> itself, validated; anything else is a ValueError."""
+def as_config(word, value, cls):
+    """The option `word` of a session, or of a check, as its configuration: None / False -> None, True -> the defaults, a `cls`
+    (a NamedTuple with a validated() method) -> itself, validated; anything else is a ValueError headed by `word`."""
     if value is None or value is False:
         return None
     if value is True:
         return cls()
     if not isinstance(value, cls):
-        raise ValueError(f"{cls.__name__.lower()}: True or a geometry.{cls.__name__}({', '.join(cls._fields)}) expected, got {type(value).__name__}")
+        raise ValueError(f"{word}: True or a {cls.__module__.rpartition('.')[2]}.{cls.__name__}({', '.join(cls._fields)}) expected, "
+                         f"got {type(value).__name__}")
     return value.validated()
 
 
@@ -108,7 +110,7 @@ class EpiResult(NamedTuple):
 
 def as_epipolar(epipolar) -> Optional[Epipolar]:
     """None / False -> None, True -> the defaults, an Epipolar -> itself, validated; anything else is a ValueError."""
-    return _as_config(epipolar, Epipolar)
+    return as_config("epipolar", epipolar, Epipolar)
 
 
 class _RansacCheck:
@@ -119,7 +121,7 @@ class _RansacCheck:
 
     def __init__(self, config=True):
         cls, a = self._config.__name__, "an" if self._config.__name__[0] in "AEIOU" else "a"
-        self.config = _as_config(config, self._config)
+        self.config = as_config(cls.lower(), config, self._config)
         if self.config is None:
             raise ValueError(f"{cls.lower()}: {a} {type(self).__name__} needs a configuration: True or {a} {cls}(...)")
         self.epoch = None      # the int32 word on the device; made by the first call
@@ -205,7 +207,7 @@ class HomResult(NamedTuple):
 
 def as_homography(homography) -> Optional[Homography]:
     """None / False -> None, True -> the defaults, a Homography -> itself, validated; anything else is a ValueError."""
-    return _as_config(homography, Homography)
+    return as_config("homography", homography, Homography)
 
 
 class HomographyCheck(_RansacCheck):

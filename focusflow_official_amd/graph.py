@@ -3,7 +3,11 @@
 One forward is ~700 small launches (8.8 ms of host time); at small batch the GPU finishes sooner than
 the host can issue them.  Every libfocusflow_hip entry point only enqueues work on the current stream
 (no allocation, no synchronisation), so the whole step is capturable: torch.cuda.CUDAGraph is a
-hipGraph on ROCm and its graph-aware allocator provides the intermediate buffers."""
+hipGraph on ROCm and its graph-aware allocator provides the intermediate buffers.  CapturedStep is the
+capture-and-replay procedure itself (warm-up, capture, the range guard around a replay); GraphedForward
+is the model's forward under it, and frames.FrameSequence puts a whole video step under it."""
+import contextlib
+
 import torch
 
 from . import ops
@@ -15,6 +19,59 @@ def require_mask_reader(model):
         raise ValueError(f"keypoints= given to {type(model).__name__}, which reads no key-point mask here: plain RAFT (use_fusion=None) "
                          "takes no mask, and models other than FF_RAFT_FUSION are not supported by these session classes "
                          "(give FF-PWC the detector's mask like any other mask)")
+
+
+class CapturedStep:
+    """`step()` - work that only enqueues on the current stream - as one hipGraph, with the always-on range guard of ops around it.
+    The one capture-and-replay procedure of GraphedForward and frames.FrameSequence.
+
+    capture(step, put_back): `warmup` steps on a side stream (they pack weights, set kernel attributes, decide the routes - exact
+    context convolutions or not - and warm the allocator) with no capture words set; `put_back()` there, which undoes what the
+    warm-up changed (a caller that has to save state for it does so before it calls capture); ops.guard_check(sync=True); then
+    the capture under ops.guard_capture: the probes of a captured forward go to a static pair of words (zeroed by a captured
+    fill).  One pair per entry of `labels`: the step's first forward fills the first, and a step with further forwards runs the
+    k-th of them inside `with self.guard(k):`.
+    replay(): ops.guard_check (raises if an earlier replay left the split formats' range), the replay, and every pair copied to
+    the host under its label for the asynchronous look at the next call (ops.guard_queue, with `owner` = the RAFT module).  -> out
+    It keeps neither `step` nor `put_back`: they are its user's methods or closures, and a reference back would leave the
+    hipGraph to the garbage collector, which may run inside somebody's capture, where a graph cannot be destroyed."""
+
+    def __init__(self, device, labels, owner):
+        self.device, self.labels, self.owner = device, labels, owner
+        self.graph = self.out = None
+        self._words, self._capturing = [None] * len(labels), False
+
+    def guard(self, k):
+        """Around the k-th further forward of the step: its own pair of words while THIS step is being captured; otherwise (a
+        warm-up step, an eager session) the thread's capture words stay as they are."""
+        return ops.guard_capture(self._words[k]) if self._capturing else contextlib.nullcontext()
+
+    def capture(self, step, put_back, warmup=3):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(warmup):
+                step()
+            put_back()
+        torch.cuda.current_stream().wait_stream(side)
+        ops.guard_check(sync=True)
+        if ops.RANGE_GUARD:
+            self._words = [torch.zeros(2, dtype=torch.int32, device=self.device) for _ in self.labels]
+        self.graph, self._capturing = torch.cuda.CUDAGraph(), True
+        try:
+            with ops.guard_capture(self._words[0]), torch.cuda.graph(self.graph), torch.no_grad():
+                self.out = step()
+        finally:
+            self._capturing = False
+        return self.out
+
+    def replay(self):
+        ops.guard_check()
+        self.graph.replay()
+        for words, label in zip(self._words, self.labels):
+            if words is not None:
+                ops.guard_queue(words, label, self.owner)
+        return self.out
 
 
 class GraphedForward:
@@ -59,26 +116,14 @@ class GraphedForward:
                 ops.forward_interpolate(out[0], out=self.flow_init)
             return out
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup):      # packs weights, sets kernel attributes, warms the allocator
-                step()
-            if self.flow_init is not None:
-                self.flow_init.zero_()       # (the warm-up forwards of a warm start left their own initialisation there)
-        torch.cuda.current_stream().wait_stream(side)
-        ops.guard_check(sync=True)          # the warm-up forwards decided the routes (exact context convolutions or not): capture those
-        # the always-on range guard inside a graph: the probes go to a static pair of words (zeroed by a captured fill), which
-        # every replay copies to the host for the asynchronous look at the next call
-        self._guard_words = torch.zeros(2, dtype=torch.int32, device=self.static_in[0].device) if ops.RANGE_GUARD else None
-        st = ops._guard_state()
-        st["capture_words"] = self._guard_words
-        self.graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(self.graph), torch.no_grad():
-                self.out = step()
-        finally:
-            st["capture_words"] = None
+        # (put back after the warm-up: the forwards of a warm start left their own initialisation in flow_init)
+        self._captured = CapturedStep(self.static_in[0].device, ("GraphedForward replay",), getattr(model, "flow_net", None))
+        self.out = self._captured.capture(step, self.reset, warmup)
+
+    @property
+    def graph(self):
+        """The captured torch.cuda.CUDAGraph."""
+        return self._captured.graph
 
     @property
     def mask1(self):
@@ -98,11 +143,7 @@ class GraphedForward:
                 raise ValueError("this graph was captured without a flow_init input: GraphedForward(..., flow_init=True)")
             if flow_init.data_ptr() != self.flow_init.data_ptr():
                 self.flow_init.copy_(flow_init)
-        ops.guard_check()                   # (raises if an earlier replay left the split formats' range)
-        self.graph.replay()
-        if self._guard_words is not None:
-            ops.guard_queue(self._guard_words, "GraphedForward replay", getattr(self.model, "flow_net", None))
-        return self.out
+        return self._captured.replay()
 
     def reset(self):
         """Back to a cold start: zero the flow_init buffer (a sequence boundary)."""

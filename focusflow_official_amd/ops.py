@@ -5,6 +5,7 @@ contiguous; a tensor may be a channel slice of a wider buffer (stride(2) = ld).
 torch is used for allocation and stream handles only — all arithmetic happens
 in libfocusflow_hip.so.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -664,7 +665,7 @@ def check_range(what: str = "forward pass"):
 #     below a quarter of it in one step raises FocusFlowHipError then - the flow of that pass was not valid - and arms the
 #     exact route for what follows.
 # The state lives in the per-thread policy object (two models driven from two threads do not see each other's words); hipGraph
-# captures take a caller-provided static word (graph.GraphedForward) and are checked after each replay.
+# captures probe into static words of their own (guard_capture; graph.CapturedStep makes them) and are checked after each replay.
 # Not covered: the encoders' INTERMEDIATE tensors and training tensors (debug mode FF_CHECK_RANGE=1).  FF_RANGE_GUARD=0: off.
 RANGE_GUARD = os.environ.get("FF_RANGE_GUARD", "1") != "0"
 GUARD_MARGIN = 4.0
@@ -675,6 +676,18 @@ def _guard_state():
     if st is None:
         st = policy.__dict__["_guard"] = {"words": None, "pending": [], "capture_words": None}
     return st
+
+
+@contextlib.contextmanager
+def guard_capture(words: Optional[Tensor]):
+    """Inside the block this thread's captured forwards probe into `words` (a static int32 pair, or None: no probes); on exit,
+    also by an exception, the value from before the block is back, so blocks nest."""
+    st = _guard_state()
+    outer, st["capture_words"] = st["capture_words"], words
+    try:
+        yield words
+    finally:
+        st["capture_words"] = outer
 
 
 def guard_begin(device):
@@ -970,12 +983,7 @@ def forward_interpolate(flow: Tensor, out: Optional[Tensor] = None) -> Tensor:
     if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
         raise _hip.FocusFlowHipError(f"forward_interpolate: (2,H,W) or (B,2,H,W) expected, got {tuple(flow.shape)}")
     src = flow.contiguous()
-    if out is None:
-        out = torch.empty_like(src)
-    else:
-        _require_gpu(out)
-        if out.shape != flow.shape or not out.is_contiguous():
-            raise _hip.FocusFlowHipError(f"forward_interpolate: out must be contiguous {tuple(flow.shape)}, got {tuple(out.shape)} strides {out.stride()}")
+    out = torch.empty_like(src) if out is None else _arg("forward_interpolate", "out", out, (torch.float32,), tuple(flow.shape), contiguous=True)
     b = src.shape[0] if src.dim() == 4 else 1
     h, w = src.shape[-2:]
     nbytes = _hip.load().ff_forward_interpolate_ws(b, h, w)
@@ -1005,21 +1013,13 @@ def good_features(image: Tensor, max_corners: int = 500, quality_level: float = 
     b, c, h, w = image.shape
     if w > 1 and image.stride(3) != 1:
         image = image.contiguous()
-    if out is None:
-        out = torch.empty((b, 1, h, w), dtype=torch.float32, device=image.device)
-    else:
-        _require_gpu(out)
-        if out.shape != (b, 1, h, w) or not out.is_contiguous():
-            raise _hip.FocusFlowHipError(f"good_features: out must be contiguous {(b, 1, h, w)}, got {tuple(out.shape)} strides {out.stride()}")
+    out = torch.empty((b, 1, h, w), dtype=torch.float32, device=image.device) if out is None else \
+        _arg("good_features", "out", out, (torch.float32,), (b, 1, h, w), contiguous=True)
     points = count = None
     if return_points and max_corners >= 1:
         points = torch.empty((b, max_corners, 2), dtype=torch.int32, device=image.device)
         count = torch.empty((b,), dtype=torch.int32, device=image.device)
-    nbytes = good_features_ws(b, h, w)
-    if ws is None:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=image.device)      # (an unsupported shape is refused by the call itself, with its reason)
-    elif ws.dtype != torch.uint8 or ws.device != image.device or not ws.is_contiguous() or ws.numel() < nbytes:
-        raise _hip.FocusFlowHipError(f"good_features: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {image.device}")
+    ws = _workspace("good_features", ws, good_features_ws(b, h, w), image.device)
     _hip.call("ff_good_features", _p(image), c, image.stride(0), image.stride(1), image.stride(2), b, h, w, int(max_corners),
               float(quality_level), int(min_distance), _p(ws), _p(out), _p(points), _p(count), _stream())
     return (out, points, count) if return_points else out
@@ -1032,21 +1032,53 @@ def pad_offsets(h: int, w: int, pad_mode: str = "sintel"):
     return pad_w // 2, (pad_h // 2 if pad_mode == "sintel" else 0), h + pad_h, w + pad_w
 
 
-def _require_device(t: Tensor, name: str, what: str, dtypes):
+# ---- the arguments of the session wrappers -----------------------------------------------------------------------------------
+def _arg(name: str, what: str, t, dtypes, shape=None, device=None, contiguous: bool = False) -> Tensor:
+    """The one check of a tensor argument: `what` of the entry `name` must be a tensor on a HIP device with one of `dtypes` and,
+    where given, of `shape` (an int per dimension, or a letter for a size that is free: ("B", "N", 2)), on `device`, contiguous.
+    -> t, or a FocusFlowHipError that names the entry, the argument, all that was asked and what came."""
     if not isinstance(t, Tensor) or not t.is_cuda:
         raise _hip.FocusFlowHipError(f"{name}: {what} must be a tensor on a HIP device (got {'a CPU tensor' if isinstance(t, Tensor) else type(t).__name__}); "
                                      "there is no CPU fallback")
-    if t.dtype not in dtypes:
-        raise _hip.FocusFlowHipError(f"{name}: {what} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    fits = shape is None or (t.dim() == len(shape) and all(isinstance(s, str) or s == d for s, d in zip(shape, t.shape)))
+    if t.dtype not in dtypes or not fits or (device is not None and t.device != device) or (contiguous and not t.is_contiguous()):
+        asked = ("contiguous " if contiguous else "") + " or ".join(str(d) for d in dtypes)
+        asked += "" if shape is None else " (" + ",".join(str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+        raise _hip.FocusFlowHipError(f"{name}: {what} must be {asked}{'' if device is None else f' on {device}'}, "
+                                     f"got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    return t
 
 
-def _padded_out(name: str, out: Optional[Tensor], shape, device) -> Tensor:
+def _outs(name: str, out, specs, device):
+    """out: None (new tensors) or one contiguous tensor per (what, shape, dtype) of `specs`, on `device`.  -> the tuple"""
     if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    _require_device(out, name, "out", (torch.float32,))
-    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
-        raise _hip.FocusFlowHipError(f"{name}: out must be contiguous {tuple(shape)} on {device}, got {tuple(out.shape)} strides {out.stride()} on {out.device}")
-    return out
+        return tuple(torch.empty(shape, dtype=dtype, device=device) for _, shape, dtype in specs)
+    if not isinstance(out, (tuple, list)) or len(out) != len(specs):
+        raise _hip.FocusFlowHipError(f"{name}: out must be the tuple ({', '.join(w for w, _, _ in specs)})")
+    return tuple(_arg(name, f"out ({what})", t, (dtype,), tuple(shape), device, contiguous=True) for t, (what, shape, dtype) in zip(out, specs))
+
+
+def _out(name: str, out: Optional[Tensor], shape, device, dtype=torch.float32) -> Tensor:
+    """out: None (a new tensor) or the contiguous `dtype` tensor of `shape` on `device` to write into."""
+    return torch.empty(shape, dtype=dtype, device=device) if out is None else _arg(name, "out", out, (dtype,), tuple(shape), device, contiguous=True)
+
+
+def _workspace(name: str, ws: Optional[Tensor], nbytes: int, device) -> Tensor:
+    """ws: None (a new one) or a contiguous uint8 tensor of at least `nbytes` bytes on `device` to work in."""
+    if ws is None:
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)      # (an unsupported shape is refused by the call itself, with its reason)
+    if _arg(name, "ws", ws, (torch.uint8,), None, device, contiguous=True).numel() < nbytes:
+        raise _hip.FocusFlowHipError(f"{name}: ws must hold at least {nbytes} bytes, got {ws.numel()}")
+    return ws
+
+
+def _frame_in_field(name: str, what: str, t, left, top, h=None, w=None, shape=("B", 2, "Hp", "Wp"), device=None):
+    """A padded (B,2,Hp,Wp) fp32 flow field of any strides whose h x w frame starts at (left, top) (default: everything right of
+    and below it), as every C entry takes it: -> (pointer, the four element strides, B, left, top, h, w, Hp, Wp).  Checks the
+    field's shape; whether the frame lies inside the field is the library's to refuse."""
+    b, _, hp, wp = _arg(name, what, t, (torch.float32,), shape, device).shape
+    left, top = int(left), int(top)
+    return (_p(t), *t.stride(), b, left, top, hp - top if h is None else int(h), wp - left if w is None else int(w), hp, wp)
 
 
 def frame_ingest(frame: Tensor, layout: str = "hwc", order: str = "rgb", pad_mode: str = "sintel", out: Optional[Tensor] = None) -> Tensor:
@@ -1055,7 +1087,7 @@ def frame_ingest(frame: Tensor, layout: str = "hwc", order: str = "rgb", pad_mod
     frame: uint8 (B,H,W,3) / (H,W,3) for layout 'hwc', (B,3,H,W) / (3,H,W) for 'chw', any strides (a crop, the [..., :3]
     view of an RGBA frame); order 'rgb' or 'bgr'; out: a contiguous fp32 (B,3,Hp,Wp) tensor (default: a new one).
     Enqueues only, so it can be captured."""
-    _require_device(frame, "frame_ingest", "frame", (torch.uint8,))
+    _arg("frame_ingest", "frame", frame, (torch.uint8,))
     if layout not in ("hwc", "chw"):
         raise _hip.FocusFlowHipError(f"frame_ingest: layout = {layout!r} ('hwc' or 'chw')")
     if order not in ("rgb", "bgr"):
@@ -1074,7 +1106,7 @@ def frame_ingest(frame: Tensor, layout: str = "hwc", order: str = "rgb", pad_mod
         raise _hip.FocusFlowHipError(f"frame_ingest: frame has {c} channels in layout {layout!r}, shape {tuple(frame.shape)}: 3 expected "
                                      "(take frame[..., :3] of an RGBA frame)")
     left, top, hp, wp = pad_offsets(h, w, pad_mode)
-    out = _padded_out("frame_ingest", out, (b, 3, hp, wp), frame.device)
+    out = _out("frame_ingest", out, (b, 3, hp, wp), frame.device)
     _hip.call("ff_frame_ingest", _p(frame), ld_b, ld_row, ld_col, ld_c, int(order == "bgr"), b, h, w, left, top, hp, wp, _p(out), _stream())
     return out
 
@@ -1083,14 +1115,14 @@ def pad_replicate(mask: Tensor, pad_mode: str = "sintel", out: Optional[Tensor] 
     """utils.InputPadder(mask.shape, pad_mode).pad for a one-channel mask, into fp32 (csrc/frame_io.hip): mask (B,1,H,W) or
     (B,H,W), uint8 or fp32, any strides; out: a contiguous fp32 (B,1,Hp,Wp) tensor (default: a new one).  Bit-identical to
     F.pad(mask.float(), mode='replicate').  Enqueues only, so it can be captured."""
-    _require_device(mask, "pad_replicate", "mask", (torch.uint8, torch.float32))
+    _arg("pad_replicate", "mask", mask, (torch.uint8, torch.float32))
     if mask.dim() == 4 and mask.shape[1] == 1:
         mask = mask[:, 0]
     if mask.dim() != 3:
         raise _hip.FocusFlowHipError(f"pad_replicate: mask must be (B,1,H,W) or (B,H,W), got {tuple(mask.shape)}")
     b, h, w = mask.shape
     left, top, hp, wp = pad_offsets(h, w, pad_mode)
-    out = _padded_out("pad_replicate", out, (b, 1, hp, wp), mask.device)
+    out = _out("pad_replicate", out, (b, 1, hp, wp), mask.device)
     _hip.call("ff_pad_replicate", _p(mask), int(mask.dtype == torch.uint8), mask.stride(0), mask.stride(1), mask.stride(2), b, h, w, left, top, hp, wp,
               _p(out), _stream())
     return out
@@ -1103,61 +1135,32 @@ def keypoint_matches(points: Tensor, count: Tensor, flow_up: Tensor, left: int, 
     strides, the padded field whose frame starts at (left, top).  -> (matches (B,N,4) fp32 [x, y, x + u, y + v], valid (B,N)
     uint8: the target lies inside the frame); rows from count[b] on hold -1 and 0.  out / valid: contiguous tensors to
     write into (default: new ones).  Enqueues only, so it can be captured."""
-    _require_device(points, "keypoint_matches", "points", (torch.int32,))
-    _require_device(count, "keypoint_matches", "count", (torch.int32,))
-    _require_device(flow_up, "keypoint_matches", "flow_up", (torch.float32,))
-    if points.dim() != 3 or points.shape[2] != 2 or not points.is_contiguous():
-        raise _hip.FocusFlowHipError(f"keypoint_matches: points must be contiguous (B,N,2), got {tuple(points.shape)} strides {points.stride()}")
-    b, n, _ = points.shape
-    if tuple(count.shape) != (b,) or not count.is_contiguous():
-        raise _hip.FocusFlowHipError(f"keypoint_matches: count must be contiguous ({b},), got {tuple(count.shape)}")
-    if flow_up.dim() != 4 or flow_up.shape[0] != b or flow_up.shape[1] != 2:
-        raise _hip.FocusFlowHipError(f"keypoint_matches: flow_up must be ({b},2,Hp,Wp), got {tuple(flow_up.shape)}")
-    hp, wp = flow_up.shape[2:]
-    if out is None:
-        out = torch.empty((b, n, 4), dtype=torch.float32, device=points.device)
-    else:
-        _require_device(out, "keypoint_matches", "out", (torch.float32,))
-        if tuple(out.shape) != (b, n, 4) or not out.is_contiguous():
-            raise _hip.FocusFlowHipError(f"keypoint_matches: out must be contiguous {(b, n, 4)}, got {tuple(out.shape)} strides {out.stride()}")
-    if valid is None:
-        valid = torch.empty((b, n), dtype=torch.uint8, device=points.device)
-    else:
-        _require_device(valid, "keypoint_matches", "valid", (torch.uint8,))
-        if tuple(valid.shape) != (b, n) or not valid.is_contiguous():
-            raise _hip.FocusFlowHipError(f"keypoint_matches: valid must be contiguous {(b, n)}, got {tuple(valid.shape)} strides {valid.stride()}")
-    _hip.call("ff_keypoint_matches", _p(points), _p(count), n, _p(flow_up), flow_up.stride(0), flow_up.stride(1), flow_up.stride(2), flow_up.stride(3),
-              b, int(left), int(top), int(h), int(w), hp, wp, _p(out), _p(valid), _stream())
+    name = "keypoint_matches"
+    b, n, _ = _arg(name, "points", points, (torch.int32,), ("B", "N", 2), contiguous=True).shape
+    dev = points.device
+    _arg(name, "count", count, (torch.int32,), (b,), contiguous=True)
+    field = _frame_in_field(name, "flow_up", flow_up, left, top, h, w, shape=(b, 2, "Hp", "Wp"))
+    out = _out(name, out, (b, n, 4), dev)
+    valid = torch.empty((b, n), dtype=torch.uint8, device=dev) if valid is None else _arg(name, "valid", valid, (torch.uint8,), (b, n), dev, contiguous=True)
+    _hip.call("ff_keypoint_matches", _p(points), _p(count), n, *field, _p(out), _p(valid), _stream())
     return out, valid
 
 
 def _track_table(name: str, pos: Tensor, ids: Tensor, age: Optional[Tensor] = None):
     """The shapes of a track table's state (tracks.TrackTable): -> (B, N)."""
-    _require_device(pos, name, "pos", (torch.float32,))
-    _require_device(ids, name, "ids", (torch.int64,))
-    if pos.dim() != 3 or pos.shape[2] != 2 or not pos.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: pos must be contiguous (B,N,2), got {tuple(pos.shape)} strides {pos.stride()}")
-    b, n, _ = pos.shape
-    if tuple(ids.shape) != (b, n) or not ids.is_contiguous() or ids.device != pos.device:
-        raise _hip.FocusFlowHipError(f"{name}: ids must be contiguous {(b, n)} on {pos.device}, got {tuple(ids.shape)} strides {ids.stride()} on {ids.device}")
+    b, n, _ = _arg(name, "pos", pos, (torch.float32,), ("B", "N", 2), contiguous=True).shape
+    _arg(name, "ids", ids, (torch.int64,), (b, n), pos.device, contiguous=True)
     if age is not None:
-        _require_device(age, name, "age", (torch.int32,))
-        if tuple(age.shape) != (b, n) or not age.is_contiguous() or age.device != pos.device:
-            raise _hip.FocusFlowHipError(f"{name}: age must be contiguous {(b, n)} on {pos.device}, got {tuple(age.shape)} strides {age.stride()} on {age.device}")
+        _arg(name, "age", age, (torch.int32,), (b, n), pos.device, contiguous=True)
     return b, n
 
 
 def _match_rows(name: str, matches: Tensor, valid: Tensor, table):
     """What fb_matches, epipolar_ransac and homography_ransac ask of a matches / valid pair and of table: None or the (pos, ids,
     age) of a track table whose slots are the rows.  -> (B, N, device, pos, ids, age)"""
-    _require_device(matches, name, "matches", (torch.float32,))
-    _require_device(valid, name, "valid", (torch.uint8,))
-    if matches.dim() != 3 or matches.shape[2] != 4 or not matches.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: matches must be contiguous (B,N,4), got {tuple(matches.shape)} strides {matches.stride()}")
-    b, n, _ = matches.shape
+    b, n, _ = _arg(name, "matches", matches, (torch.float32,), ("B", "N", 4), contiguous=True).shape
     dev = matches.device
-    if tuple(valid.shape) != (b, n) or not valid.is_contiguous() or valid.device != dev:
-        raise _hip.FocusFlowHipError(f"{name}: valid must be contiguous {(b, n)} on {dev}, got {tuple(valid.shape)} strides {valid.stride()} on {valid.device}")
+    _arg(name, "valid", valid, (torch.uint8,), (b, n), dev, contiguous=True)
     pos = ids = age = None
     if table is not None:
         if not isinstance(table, (tuple, list)) or len(table) != 3 or any(t is None for t in table):
@@ -1166,19 +1169,6 @@ def _match_rows(name: str, matches: Tensor, valid: Tensor, table):
         if _track_table(name, pos, ids, age) != (b, n) or pos.device != dev:
             raise _hip.FocusFlowHipError(f"{name}: table must have the rows of matches, {(b, n)} on {dev}, got pos {tuple(pos.shape)} on {pos.device}")
     return b, n, dev, pos, ids, age
-
-
-def _track_outs(name: str, out, specs, device):
-    """out: None (new tensors) or one contiguous tensor per (what, shape, dtype) of `specs`, on `device`."""
-    if out is None:
-        return tuple(torch.empty(shape, dtype=dtype, device=device) for _, shape, dtype in specs)
-    if not isinstance(out, (tuple, list)) or len(out) != len(specs):
-        raise _hip.FocusFlowHipError(f"{name}: out must be the tuple ({', '.join(w for w, _, _ in specs)})")
-    for t, (what, shape, dtype) in zip(out, specs):
-        _require_device(t, name, f"out ({what})", (dtype,))
-        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
-            raise _hip.FocusFlowHipError(f"{name}: out ({what}) must be contiguous {tuple(shape)} on {device}, got {tuple(t.shape)} strides {t.stride()} on {t.device}")
-    return tuple(out)
 
 
 def tracks_replenish(pos: Tensor, ids: Tensor, age: Tensor, next_id: Tensor, points: Tensor, count: Tensor, h: int, w: int,
@@ -1191,19 +1181,10 @@ def tracks_replenish(pos: Tensor, ids: Tensor, age: Tensor, next_id: Tensor, poi
     into (default: new tensors).  Exact.  Enqueues only, so it can be captured."""
     name = "tracks_replenish"
     b, n = _track_table(name, pos, ids, age)
-    _require_device(next_id, name, "next_id", (torch.int64,))
-    _require_device(points, name, "points", (torch.int32,))
-    _require_device(count, name, "count", (torch.int32,))
-    for t, what in ((next_id, "next_id"), (points, "points"), (count, "count")):
-        if t.device != pos.device:
-            raise _hip.FocusFlowHipError(f"{name}: {what} is on {t.device}, the table on {pos.device}: one device expected")
-    if tuple(next_id.shape) != (b,) or not next_id.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: next_id must be contiguous ({b},), got {tuple(next_id.shape)}")
-    if points.dim() != 3 or points.shape[0] != b or points.shape[2] != 2 or not points.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: points must be contiguous ({b},M,2), got {tuple(points.shape)} strides {points.stride()}")
-    if tuple(count.shape) != (b,) or not count.is_contiguous():
-        raise _hip.FocusFlowHipError(f"{name}: count must be contiguous ({b},), got {tuple(count.shape)}")
-    born, live = _track_outs(name, out, (("born", (b,), torch.int32), ("live", (b,), torch.int32)), pos.device)
+    _arg(name, "next_id", next_id, (torch.int64,), (b,), pos.device, contiguous=True)
+    _arg(name, "points", points, (torch.int32,), (b, "M", 2), pos.device, contiguous=True)
+    _arg(name, "count", count, (torch.int32,), (b,), pos.device, contiguous=True)
+    born, live = _outs(name, out, (("born", (b,), torch.int32), ("live", (b,), torch.int32)), pos.device)
     _hip.call("ff_tracks_replenish", _p(pos), _p(ids), _p(age), _p(next_id), n, _p(points), _p(count), points.shape[1], b, int(h), int(w),
               int(min_distance), _p(born), _p(live), _stream())
     return born, live
@@ -1214,7 +1195,7 @@ def tracks_mask(pos: Tensor, ids: Tensor, h: int, w: int, out: Optional[Tensor] 
     every live slot's position (floorf(x + 0.5f), clamped into the frame).  out: a contiguous (B,1,h,w) fp32 tensor (default: a
     new one).  Enqueues only, so it can be captured."""
     b, _ = _track_table("tracks_mask", pos, ids)
-    out = _padded_out("tracks_mask", out, (b, 1, int(h), int(w)), pos.device)
+    out = _out("tracks_mask", out, (b, 1, int(h), int(w)), pos.device)
     _hip.call("ff_tracks_mask", _p(pos), _p(ids), pos.shape[1], b, int(h), int(w), _p(out), _stream())
     return out
 
@@ -1228,24 +1209,11 @@ def tracks_advance(pos: Tensor, ids: Tensor, age: Tensor, flow_up: Tensor, left:
     Exact.  Enqueues only, so it can be captured."""
     name = "tracks_advance"
     b, n = _track_table(name, pos, ids, age)
-    _require_device(flow_up, name, "flow_up", (torch.float32,))
-    if flow_up.dim() != 4 or flow_up.shape[0] != b or flow_up.shape[1] != 2 or flow_up.device != pos.device:
-        raise _hip.FocusFlowHipError(f"{name}: flow_up must be ({b},2,Hp,Wp) on {pos.device}, got {tuple(flow_up.shape)} on {flow_up.device}")
-    hp, wp = flow_up.shape[2:]
-    matches, valid, ids_out, age_out = _track_outs(name, out, (("matches", (b, n, 4), torch.float32), ("valid", (b, n), torch.uint8),
-                                                               ("ids", (b, n), torch.int64), ("age", (b, n), torch.int32)), pos.device)
-    _hip.call("ff_tracks_advance", _p(pos), _p(ids), _p(age), n, _p(flow_up), flow_up.stride(0), flow_up.stride(1), flow_up.stride(2), flow_up.stride(3),
-              b, int(left), int(top), int(h), int(w), hp, wp, _p(matches), _p(valid), _p(ids_out), _p(age_out), _stream())
+    field = _frame_in_field(name, "flow_up", flow_up, left, top, h, w, shape=(b, 2, "Hp", "Wp"), device=pos.device)
+    matches, valid, ids_out, age_out = _outs(name, out, (("matches", (b, n, 4), torch.float32), ("valid", (b, n), torch.uint8),
+                                                         ("ids", (b, n), torch.int64), ("age", (b, n), torch.int32)), pos.device)
+    _hip.call("ff_tracks_advance", _p(pos), _p(ids), _p(age), n, *field, _p(matches), _p(valid), _p(ids_out), _p(age_out), _stream())
     return matches, valid, ids_out, age_out
-
-
-def _fb_field(name: str, t: Tensor, what: str, b: Optional[int], device):
-    """A padded (B,2,Hp,Wp) fp32 flow field of any strides: -> (B, Hp, Wp)."""
-    _require_device(t, name, what, (torch.float32,))
-    if t.dim() != 4 or t.shape[1] != 2 or (b is not None and t.shape[0] != b) or (device is not None and t.device != device):
-        raise _hip.FocusFlowHipError(f"{name}: {what} must be ({'B' if b is None else b},2,Hp,Wp)" + (f" on {device}" if device is not None else "")
-                                     + f", got {tuple(t.shape)} on {t.device}")
-    return t.shape[0], t.shape[2], t.shape[3]
 
 
 def fb_dense(fw: Tensor, bw: Tensor, left: int, top: int, h: int, w: int, alpha: float = 0.01, beta: float = 0.5, out=None):
@@ -1256,13 +1224,11 @@ def fb_dense(fw: Tensor, bw: Tensor, left: int, top: int, h: int, w: int, alpha:
     fp32, +inf outside the frame; occluded (B,1,h,w) uint8, 1 or 0); out: that tuple to write into (default: new tensors).
     Exact.  Enqueues only, so it can be captured."""
     name = "fb_dense"
-    b, hp, wp = _fb_field(name, fw, "fw", None, None)
-    _fb_field(name, bw, "bw", b, fw.device)
-    if tuple(bw.shape[2:]) != (hp, wp):
-        raise _hip.FocusFlowHipError(f"{name}: bw must be ({b},2,{hp},{wp}) as fw is, got {tuple(bw.shape)}")
-    err2, occluded = _track_outs(name, out, (("err2", (b, 1, int(h), int(w)), torch.float32), ("occluded", (b, 1, int(h), int(w)), torch.uint8)), fw.device)
-    _hip.call("ff_fb_dense", _p(fw), fw.stride(0), fw.stride(1), fw.stride(2), fw.stride(3), _p(bw), bw.stride(0), bw.stride(1), bw.stride(2), bw.stride(3),
-              b, int(left), int(top), int(h), int(w), hp, wp, float(alpha), float(beta), _p(err2), _p(occluded), _stream())
+    fw_field = _frame_in_field(name, "fw", fw, left, top, h, w)
+    b, _, _, h, w, hp, wp = fw_field[5:]
+    bw_field = _frame_in_field(name, "bw", bw, left, top, h, w, shape=(b, 2, hp, wp), device=fw.device)
+    err2, occluded = _outs(name, out, (("err2", (b, 1, h, w), torch.float32), ("occluded", (b, 1, h, w), torch.uint8)), fw.device)
+    _hip.call("ff_fb_dense", *fw_field[:5], *bw_field, float(alpha), float(beta), _p(err2), _p(occluded), _stream())
     return err2, occluded
 
 
@@ -1277,10 +1243,9 @@ def fb_matches(matches: Tensor, valid: Tensor, bw: Tensor, left: int, top: int, 
     inconsistent); out: that tuple to write into (default: new tensors).  Exact.  Enqueues only, so it can be captured."""
     name = "fb_matches"
     b, n, dev, pos, ids, age = _match_rows(name, matches, valid, table)
-    _, hp, wp = _fb_field(name, bw, "bw", b, dev)
-    err2, status = _track_outs(name, out, (("err2", (b, n), torch.float32), ("status", (b, n), torch.uint8)), dev)
-    _hip.call("ff_fb_matches", _p(matches), _p(valid), n, _p(bw), bw.stride(0), bw.stride(1), bw.stride(2), bw.stride(3), b, int(left), int(top), int(h),
-              int(w), hp, wp, float(alpha), float(beta), _p(pos), _p(ids), _p(age), _p(err2), _p(status), _stream())
+    field = _frame_in_field(name, "bw", bw, left, top, h, w, shape=(b, 2, "Hp", "Wp"), device=dev)
+    err2, status = _outs(name, out, (("err2", (b, n), torch.float32), ("status", (b, n), torch.uint8)), dev)
+    _hip.call("ff_fb_matches", _p(matches), _p(valid), n, *field, float(alpha), float(beta), _p(pos), _p(ids), _p(age), _p(err2), _p(status), _stream())
     return err2, status
 
 
@@ -1299,10 +1264,9 @@ def flow_to_image(flow: Tensor, left: int = 0, top: int = 0, h: Optional[int] = 
     return_max (image, rad_max (B) fp32: the maxima of the frames, whether or not max_flow replaced them as the scale).  Two
     launches (one with max_flow and without return_max); enqueues only, so it can be captured."""
     name = "flow_to_image"
-    b, hp, wp = _fb_field(name, flow, "flow", None, None)
+    field = _frame_in_field(name, "flow", flow, left, top, h, w)
+    b, left, top, h, w, hp, wp = field[5:]
     dev = flow.device
-    left, top = int(left), int(top)
-    h, w = hp - top if h is None else int(h), wp - left if w is None else int(w)
     if left < 0 or top < 0 or h < 1 or w < 1 or left + w > wp or top + h > hp:
         raise _hip.FocusFlowHipError(f"{name}: the {h} x {w} frame at (left, top) = ({left}, {top}) does not lie inside the {hp} x {wp} field")
     if max_flow is not None and not (float(max_flow) > 0 and math.isfinite(float(max_flow))):
@@ -1315,12 +1279,9 @@ def flow_to_image(flow: Tensor, left: int = 0, top: int = 0, h: Optional[int] = 
         raise _hip.FocusFlowHipError(f"{name}: layout = {layout!r} ('hwc' or 'chw')")
     occ_ld = (0, 0, 0)
     if occluded is not None:
-        _require_device(occluded, name, "occluded", (torch.uint8,))
-        if occluded.dim() == 4 and occluded.shape[1] == 1:
+        if isinstance(occluded, Tensor) and occluded.dim() == 4 and occluded.shape[1] == 1:      # (B,1,h,w) is taken as (B,h,w)
             occluded = occluded[:, 0]
-        if tuple(occluded.shape) != (b, h, w) or occluded.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: occluded must be ({b},1,{h},{w}) or ({b},{h},{w}) on {dev}, got {tuple(occluded.shape)} on {occluded.device}")
-        occ_ld = occluded.stride()
+        occ_ld = _arg(name, "occluded", occluded, (torch.uint8,), (b, h, w), dev).stride()
     try:
         color = tuple(int(c) for c in occluded_color)
         exact = all(c == x for c, x in zip(color, occluded_color))
@@ -1334,18 +1295,10 @@ def flow_to_image(flow: Tensor, left: int = 0, top: int = 0, h: Optional[int] = 
         if not return_max or len(out) != 2:
             raise _hip.FocusFlowHipError(f"{name}: out must be the image, or with return_max the tuple (image, rad_max)")
         out, rad_max = out
-        _require_device(rad_max, name, "out (rad_max)", (torch.float32,))
-        if tuple(rad_max.shape) != (b,) or not rad_max.is_contiguous() or rad_max.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: out (rad_max) must be contiguous ({b},) on {dev}, got {tuple(rad_max.shape)} on {rad_max.device}")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=dev)
-    else:
-        _require_device(out, name, "out", (torch.uint8,))
-        if tuple(out.shape) != shape or out.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: out must be {shape} for layout {layout!r} on {dev}, got {tuple(out.shape)} on {out.device}")
+        _arg(name, "out (rad_max)", rad_max, (torch.float32,), (b,), dev, contiguous=True)
+    out = torch.empty(shape, dtype=torch.uint8, device=dev) if out is None else _arg(name, f"out (layout {layout!r})", out, (torch.uint8,), shape, dev)
     ld_b, ld_row, ld_col, ld_c = out.stride() if layout == "hwc" else (out.stride(0), out.stride(2), out.stride(3), out.stride(1))
     clip = -1.0 if clip_flow is None else float(clip_flow)
-    field = (_p(flow), flow.stride(0), flow.stride(1), flow.stride(2), flow.stride(3), b, left, top, h, w, hp, wp)
     if max_flow is None or return_max:
         if rad_max is None:
             rad_max = torch.empty((b,), dtype=torch.float32, device=dev)
@@ -1366,27 +1319,17 @@ def _ransac(check: str, model: str, matches: Tensor, valid: Tensor, h, w, thresh
     (B,3,3) output; permilles: (permille,), or (permille, planar_permille) for a check with a `planar` output.  -> the outputs"""
     name = f"{check}_ransac"
     b, n, dev, pos, ids, age = _match_rows(name, matches, valid, table)
-    _require_device(epoch, name, "epoch", (torch.int32,))
-    if epoch.numel() != 1 or epoch.device != dev:
-        raise _hip.FocusFlowHipError(f"{name}: epoch must be one int32 on {dev}, got {tuple(epoch.shape)} on {epoch.device}")
+    if _arg(name, "epoch", epoch, (torch.int32,), None, dev).numel() != 1:
+        raise _hip.FocusFlowHipError(f"{name}: epoch must be one int32, got {tuple(epoch.shape)}")
     if check == "homography" and matches.data_ptr() % 16:
         raise _hip.FocusFlowHipError(f"{name}: matches must be 16-byte aligned (a view that starts inside a row is not)")
     per_sample = [("inliers", torch.int32), ("candidates", torch.int32), ("ok", torch.uint8)] + [("planar", torch.uint8)] * (len(permilles) == 2)
-    res = _track_outs(name, out, ((model, (b, 3, 3), torch.float32), *((what, (b,), dtype) for what, dtype in per_sample),
-                                  ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
-    nbytes = getattr(_hip.load(), f"ff_{check}_ws")(b, n, int(hypotheses))
-    if ws is None:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)      # (an unsupported shape is refused by the call itself, with its reason)
-    else:
-        _require_device(ws, name, "ws", (torch.uint8,))
-        if ws.numel() < nbytes or not ws.is_contiguous() or ws.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: ws must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}, got {ws.numel()} on {ws.device}")
+    res = _outs(name, out, ((model, (b, 3, 3), torch.float32), *((what, (b,), dtype) for what, dtype in per_sample),
+                            ("status", (b, n), torch.uint8), ("dist2", (b, n), torch.float32)), dev)
+    ws = _workspace(name, ws, getattr(_hip.load(), f"ff_{check}_ws")(b, n, int(hypotheses)), dev)
     entry, tail = f"ff_{check}_ransac", ()
     if hold is not None:
-        _require_device(hold, name, "hold", (torch.uint8,))
-        if tuple(hold.shape) != (b,) or not hold.is_contiguous() or hold.device != dev:
-            raise _hip.FocusFlowHipError(f"{name}: hold must be contiguous {(b,)} on {dev}, got {tuple(hold.shape)} on {hold.device}")
-        entry, tail = entry + "_hold", (_p(hold),)
+        entry, tail = entry + "_hold", (_p(_arg(name, "hold", hold, (torch.uint8,), (b,), dev, contiguous=True)),)
     m3, *per_sample, status, dist2 = res      # (the C entries take dist2 and status before the per-sample outputs)
     _hip.call(entry, _p(matches), _p(valid), b, n, int(h), int(w), float(threshold), int(hypotheses), int(min_inliers), *map(int, permilles),
               int(seed) & 0xffffffff, _p(epoch), int(bool(cull)), _p(pos), _p(ids), _p(age), _p(m3), _p(dist2), _p(status), *map(_p, per_sample), _p(ws),
@@ -1439,21 +1382,14 @@ def homography_residual(flow: Tensor, H: Tensor, ok: Tensor, out: Optional[Tenso
     in px^2, +inf where the map's w <= 0, -1 over a sample with ok = 0; out: a contiguous tensor to write into.  One launch, one
     pass.  Exact.  Enqueues only, so it can be captured."""
     name = "homography_residual"
-    _require_device(flow, name, "flow", (torch.float32,))
-    if flow.dim() != 4 or flow.shape[1] != 2 or flow.numel() == 0:
-        raise _hip.FocusFlowHipError(f"{name}: flow must be (B,2,h,w), got {tuple(flow.shape)}")
-    b, _, h, w = flow.shape
+    b, _, h, w = _arg(name, "flow", flow, (torch.float32,), ("B", 2, "h", "w")).shape
     dev = flow.device
-    _require_device(H, name, "H", (torch.float32,))
-    _require_device(ok, name, "ok", (torch.uint8,))
-    if tuple(H.shape) != (b, 3, 3) or not H.is_contiguous() or H.device != dev:
-        raise _hip.FocusFlowHipError(f"{name}: H must be contiguous {(b, 3, 3)} on {dev}, got {tuple(H.shape)} on {H.device}")
-    if tuple(ok.shape) != (b,) or not ok.is_contiguous() or ok.device != dev:
-        raise _hip.FocusFlowHipError(f"{name}: ok must be contiguous {(b,)} on {dev}, got {tuple(ok.shape)} on {ok.device}")
-    if any(s < 0 for s in flow.stride()):
-        raise _hip.FocusFlowHipError(f"{name}: flow has a negative stride: {flow.stride()}")
-    out = _padded_out(name, out, (b, h, w), dev)
-    _hip.call("ff_homography_residual", _p(flow), flow.stride(0), flow.stride(1), flow.stride(2), flow.stride(3), _p(H), _p(ok), b, h, w, _p(out), _stream())
+    if flow.numel() == 0 or any(s < 0 for s in flow.stride()):
+        raise _hip.FocusFlowHipError(f"{name}: flow must be a non-empty (B,2,h,w) without a negative stride, got {tuple(flow.shape)} strides {flow.stride()}")
+    _arg(name, "H", H, (torch.float32,), (b, 3, 3), dev, contiguous=True)
+    _arg(name, "ok", ok, (torch.uint8,), (b,), dev, contiguous=True)
+    out = _out(name, out, (b, h, w), dev)
+    _hip.call("ff_homography_residual", _p(flow), *flow.stride(), _p(H), _p(ok), b, h, w, _p(out), _stream())
     return out
 
 
@@ -1463,10 +1399,8 @@ _minus_one = {}      # device -> the one-element tensor -1.0 that negate() scale
 def negate(src: Tensor, out: Tensor) -> Tensor:
     """out = -src for two contiguous fp32 tensors of one shape: ff_scale_add_fwd with the scale -1 and no addend (sign flips are
     exact; a zero comes out as +0).  One launch, enqueues only."""
-    _require_device(src, "negate", "src", (torch.float32,))
-    _require_device(out, "negate", "out", (torch.float32,))
-    if out.shape != src.shape or not src.is_contiguous() or not out.is_contiguous() or out.device != src.device:
-        raise _hip.FocusFlowHipError(f"negate: src and out must be contiguous and of one shape on one device, got {tuple(src.shape)} and {tuple(out.shape)}")
+    _arg("negate", "src", src, (torch.float32,), contiguous=True)
+    _arg("negate", "out", out, (torch.float32,), tuple(src.shape), src.device, contiguous=True)
     key = src.device
     minus = _minus_one.get(key)
     if minus is None:      # (made once per device, outside any capture: FrameSequence asks for it when it allocates)

@@ -179,6 +179,31 @@ def test_no_cpu_fallback(lib_path):
         m(x, x, torch.zeros(1, 1, 128, 128), torch.zeros(1, 1, 128, 128), raft_iters=1, test_mode=True)
 
 
+def test_guard_capture_sets_restores_and_nests(lib_path):
+    """ops.guard_capture: inside the block the thread's capture words are the ones given; on exit the OUTER value is back, not
+    None - after a clean block, after one that raises, and at every level of a nest.  No device: two stand-ins serve as words."""
+    from focusflow_official_amd import ops
+    words = lambda: ops._guard_state()["capture_words"]      # noqa: E731
+    a, b = object(), object()
+    assert words() is None
+    with ops.guard_capture(a) as given:
+        assert given is a and words() is a
+        with ops.guard_capture(b):
+            assert words() is b
+            with ops.guard_capture(None):
+                assert words() is None
+            assert words() is b
+        assert words() is a
+        with pytest.raises(KeyError, match="inner"), ops.guard_capture(b):
+            assert words() is b
+            raise KeyError("inner")
+        assert words() is a
+    assert words() is None
+    with pytest.raises(KeyError, match="outer"), ops.guard_capture(a):
+        raise KeyError("outer")
+    assert words() is None
+
+
 def test_product_code_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "focusflow_official_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -502,6 +502,30 @@ def test_results_are_static_buffers_until_the_next_push(ffraft):
 
 
 @pytest.mark.gpu
+def test_a_captured_graph_goes_with_its_owner(ffraft):
+    """A session's and a GraphedForward's hipGraph (graph.CapturedStep) are freed by reference count when their owner goes: no
+    cycle leaves them to the garbage collector, which may run inside a later capture, where a graph cannot be destroyed."""
+    import gc
+    import weakref
+    from focusflow_official_amd.frames import FrameSequence
+    from focusflow_official_amd.graph import GraphedForward
+    from focusflow_official_amd.keypoints import GoodFeatures
+    frames = _u8_frames(1, 125, 157, frames=2, seed=7)
+    seq = FrameSequence(ffraft, raft_iters=2, keypoints=GoodFeatures(), fb=True)
+    assert seq.push(frames[0]) is None and seq.push(frames[1]) is not None
+    img = torch.zeros(1, 3, 128, 160, device=DEV)
+    gf = GraphedForward(ffraft, (img, img, torch.zeros(1, 1, 128, 160, device=DEV), None), raft_iters=2)
+    refs = [weakref.ref(seq._captured), weakref.ref(gf._captured)]
+    assert all(r().graph is not None for r in refs)
+    gc.disable()      # (a collector run between the two lines below would hide a cycle)
+    try:
+        del seq, gf
+        assert [r() for r in refs] == [None, None]
+    finally:
+        gc.enable()
+
+
+@pytest.mark.gpu
 def test_session_refusals_name_the_argument(ffraft):
     from focusflow_official_amd import FF_RAFT_FUSION
     from focusflow_official_amd._hip import FocusFlowHipError

@@ -1001,6 +1001,35 @@ def test_hipgraph_replay_matches_eager(det_sd):
     assert not torch.equal(ga[1], gb[1])
 
 
+def test_hipgraph_replay_guard_refuses_inputs_beyond_the_split_range(det_sd):
+    """The replay half of the always-on guard (graph.CapturedStep.replay: ops.guard_check, the replay, ops.guard_queue of the
+    capture's static words).  A GraphedForward captured and replayed on in-range inputs passes check_range(); a replay on the
+    same images times a power of two that lifts the model's running level (max|x| of the two guarded encoder outputs) to at
+    least 4 x the fp16-split formats' limit is refused under the capture's label, by check_range() and, for a further such
+    replay, by the call that follows it.  A refusal in Python of numbers out of range, as the eager test above provokes it."""
+    import math
+    from focusflow_official_amd import _hip, ops as hops
+    from focusflow_official_amd.graph import GraphedForward
+    m = _model(det_sd)
+    inp = [t.to(DEV) for t in orc.shifted_pair(1, 128, 160, seed=2)]
+    gf = GraphedForward(m, inp, raft_iters=2)
+    gf(*inp)
+    gf.check_range()
+    level = m.flow_net._guard_level
+    assert 1.0 < level < hops.X_LIMIT / hops.GUARD_MARGIN
+    scale = 2.0 ** math.ceil(math.log2(4 * hops.X_LIMIT / level))
+    big = [inp[0] * scale, inp[1] * scale, *inp[2:]]
+    print(f"running level {level:.6g}, limit {hops.X_LIMIT:g}: images x {scale:g}")
+    gf(*big)
+    with pytest.raises(_hip.FocusFlowHipError, match="GraphedForward replay"):
+        gf.check_range()
+    gf(*big)
+    torch.cuda.synchronize()      # (the words of that replay have arrived: the look at the start of the next call sees them)
+    with pytest.raises(_hip.FocusFlowHipError, match="GraphedForward replay"):
+        gf(*inp)
+    gf.check_range()              # (a refusal drops what was pending: nothing is left over for the tests behind this one)
+
+
 @pytest.mark.parametrize("modal", ["frame", "neighborG", "neighborE", "context"])
 def test_mask_modes(modal, det_sd):
     """init_mask modes (ff_raft.py:23-72): prepared mask tensors and the resulting flow vs the oracle."""
