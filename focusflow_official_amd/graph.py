@@ -32,14 +32,16 @@ class CapturedStep:
     fill).  One pair per entry of `labels`: the step's first forward fills the first, and a step with further forwards runs the
     k-th of them inside `with self.guard(k):`.
     replay(): ops.guard_check (raises if an earlier replay left the split formats' range), the replay, and every pair copied to
-    the host under its label for the asynchronous look at the next call (ops.guard_queue, with `owner` = the RAFT module).  -> out
+    the host under its label for the asynchronous look at the next call (ops.guard_queue, with `owner` = the RAFT module and the
+    owner's `_exact_ctx` as it stood at capture: a graph captured on the split route is refused on context features beyond the
+    range at EVERY replay, also after the first refusal armed the flag - capturing again is the caller's business).  -> out
     It keeps neither `step` nor `put_back`: they are its user's methods or closures, and a reference back would leave the
     hipGraph to the garbage collector, which may run inside somebody's capture, where a graph cannot be destroyed."""
 
     def __init__(self, device, labels, owner):
         self.device, self.labels, self.owner = device, labels, owner
         self.graph = self.out = None
-        self._words, self._capturing = [None] * len(labels), False
+        self._words, self._capturing, self._exact_ctx = [None] * len(labels), False, False
 
     def guard(self, k):
         """Around the k-th further forward of the step: its own pair of words while THIS step is being captured; otherwise (a
@@ -57,6 +59,9 @@ class CapturedStep:
         ops.guard_check(sync=True)
         if ops.RANGE_GUARD:
             self._words = [torch.zeros(2, dtype=torch.int32, device=self.device) for _ in self.labels]
+        # the route the graph holds: the owner's flag as the warm-up left it (SepConvGRU.prepare runs at capture time); every
+        # replay is judged by it, whatever the flag says by then
+        self._exact_ctx = bool(getattr(self.owner, "_exact_ctx", False))
         self.graph, self._capturing = torch.cuda.CUDAGraph(), True
         try:
             with ops.guard_capture(self._words[0]), torch.cuda.graph(self.graph), torch.no_grad():
@@ -70,7 +75,7 @@ class CapturedStep:
         self.graph.replay()
         for words, label in zip(self._words, self.labels):
             if words is not None:
-                ops.guard_queue(words, label, self.owner)
+                ops.guard_queue(words, label, self.owner, exact_ctx=self._exact_ctx)
         return self.out
 
 

@@ -139,7 +139,8 @@ class FF_RAFT_FUSION(nn.Module):
         ops.guard_begin(image1.device)       # (raises if an EARLIER forward left the split formats' range: ops.guard_check)
         self.flow_net._guard_handled = False
         out = self.flow_net(i1, i2, m1, m2, iters=raft_iters, flow_init=flow_init, test_mode=test_mode)
-        ops.guard_end("FF_RAFT_FUSION.forward", owner=self.flow_net, handled=self.flow_net._guard_handled)
+        ops.guard_end("FF_RAFT_FUSION.forward", owner=self.flow_net, handled=self.flow_net._guard_handled,
+                      exact_ctx=self.flow_net._guard_exact, recorded=self.flow_net._guard_recorded)   # (judged by the route it took)
         ops.check_range("FF_RAFT_FUSION.forward")      # debug mode FF_CHECK_RANGE=1 only (one host sync)
         return out
 

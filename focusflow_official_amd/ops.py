@@ -664,6 +664,11 @@ def check_range(what: str = "forward pass"):
 #     forward starts (or on demand: FF_RAFT_FUSION.check_range(), one host sync): a value that jumped past the limit from
 #     below a quarter of it in one step raises FocusFlowHipError then - the flow of that pass was not valid - and arms the
 #     exact route for what follows.
+# A forward is judged by the route IT took (guard_verdict), not by what the owner's `_exact_ctx` says when the look happens:
+# every queued pair of words carries that route (guard_end / guard_queue: exact_ctx, recorded).  A recorded pass has no exact
+# route, so a context output beyond the limit refuses it whether the flag is armed or not; a hipGraph captured before the
+# flag was armed holds the split route, so every replay of it on such inputs is refused (graph.CapturedStep remembers the
+# flag as it stood at capture; capturing again after the refusal gives a graph on the exact route).
 # The state lives in the per-thread policy object (two models driven from two threads do not see each other's words); hipGraph
 # captures probe into static words of their own (guard_capture; graph.CapturedStep makes them) and are checked after each replay.
 # Not covered: the encoders' INTERMEDIATE tensors and training tensors (debug mode FF_CHECK_RANGE=1).  FF_RANGE_GUARD=0: off.
@@ -734,28 +739,54 @@ def guard_note(owner, m_ctx: float, m_fmap: float):
     owner._guard_hist = True
 
 
-def guard_end(what: str, owner=None, handled: bool = False):
-    """End of a forward: queue its words for the asynchronous look (handled: a careful forward has read them already)."""
+GUARD_ADVICE_FP32 = "Run this checkpoint / input with FF_CONV_PRECISION=fp32."
+GUARD_ADVICE_RECORDED = ("The context encoder's output left the range in a RECORDED pass; the exact-fp32 repair covers inference only.  "
+                         "Train this checkpoint with FF_CONV_PRECISION=fp32.")
+GUARD_ADVICE_EXACT = "The context features' convolutions run on the exact-fp32 route from now on."
+
+
+def guard_verdict(m_ctx: float, m_fmap: float, exact_route: bool, recorded: bool = False):
+    """The guard's decision on one forward, from its two maxima and the route it TOOK (or, in a careful forward, is about to
+    take): exact_route - the context features' convolutions on the exact-fp32 rows; recorded - an autograd pass, which has no
+    exact route whatever exact_route says.  -> (refuse, arm, advice): refuse - the flow of that forward is not valid; arm - the
+    exact route repairs it (set the owner's `_exact_ctx`; a careful forward, which has not met a split convolution yet, takes
+    it at once instead of refusing); advice - the tail of the error message.  Pure: no owner, no state."""
+    if not (m_fmap < X_LIMIT) or not (m_ctx < float("inf")):
+        return True, False, GUARD_ADVICE_FP32
+    if m_ctx < X_LIMIT:
+        return False, False, ""
+    if recorded:
+        return True, False, GUARD_ADVICE_RECORDED
+    if exact_route:
+        return False, False, ""
+    return True, True, GUARD_ADVICE_EXACT
+
+
+def guard_end(what: str, owner=None, handled: bool = False, exact_ctx: bool = False, recorded: bool = False):
+    """End of a forward: queue its words for the asynchronous look (handled: a careful forward has read them already).
+    exact_ctx / recorded: the route this forward took (guard_verdict)."""
     st = _guard_state()
     w, st["words"] = st["words"], None
     if w is None or handled or torch.cuda.is_current_stream_capturing():
         return
-    guard_queue(w, what, owner)
+    guard_queue(w, what, owner, exact_ctx=exact_ctx, recorded=recorded)
 
 
-def guard_queue(words: Tensor, what: str, owner=None):
+def guard_queue(words: Tensor, what: str, owner=None, exact_ctx: bool = False, recorded: bool = False):
+    """Copy a finished forward's pair of words to the host for guard_check, with the route that forward took: it is judged by
+    that, not by what the owner's `_exact_ctx` says when the look happens."""
     host = torch.empty(2, dtype=torch.int32, pin_memory=True)
     host.copy_(words, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    _guard_state()["pending"].append((host, ev, what, owner))
+    _guard_state()["pending"].append((host, ev, what, owner, bool(exact_ctx), bool(recorded)))
 
 
 def guard_check(sync: bool = False):
     """Look at the guard words of finished forwards (all of them if sync, else those whose copy has arrived)."""
     pending = _guard_state()["pending"]
     while pending:
-        host, ev, what, owner = pending[0]
+        host, ev, what, owner, exact_ctx, recorded = pending[0]
         if not ev.query():
             if not sync:
                 return
@@ -764,16 +795,14 @@ def guard_check(sync: bool = False):
         m_ctx, m_fmap = host.view(torch.float32).tolist()
         if owner is not None:
             guard_note(owner, m_ctx, m_fmap)
-        ctx_bad = not (m_ctx < X_LIMIT) and not (getattr(owner, "_exact_ctx", False) and m_ctx < float("inf"))
-        if ctx_bad or not (m_fmap < X_LIMIT):
+        refuse, arm, advice = guard_verdict(m_ctx, m_fmap, exact_ctx, recorded)
+        if refuse:
             pending.clear()
-            if owner is not None and ctx_bad and m_ctx < float("inf"):
+            if owner is not None and arm:
                 owner._exact_ctx = True            # the next forward of this model is right
             raise _hip.FocusFlowHipError(
                 f"{what}: an encoder output reached |x| = {max(m_ctx, m_fmap):.6g}; the fp16-split conv formats need |x| < {X_LIMIT:g} "
-                "(csrc/ff_common.h) - the flow of that pass is not valid.  "
-                + ("The context features' convolutions run on the exact-fp32 route from now on." if ctx_bad and m_fmap < X_LIMIT and m_ctx < float("inf")
-                   else "Run this checkpoint / input with FF_CONV_PRECISION=fp32."))
+                "(csrc/ff_common.h) - the flow of that pass is not valid.  " + advice)
 
 
 def _zero_stats(s, c, device):

@@ -52,8 +52,10 @@ class RAFT(nn.Module):
                 self.cnet = BasicEncoder(3, output_dim=hdim + cdim, norm_fn="batch", dropout=dropout)
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=hdim)
         # the always-on range guard's memory of this model (ops.guard_*): running max|x| of the two guarded encoder outputs, and
-        # the sticky repair - the context features' convolutions on the exact-fp32 route
+        # the sticky repair - the context features' convolutions on the exact-fp32 route; and what the running forward did: looked
+        # at its words itself (handled), took the exact route, was recorded
         self._guard_hist, self._guard_level, self._exact_ctx, self._guard_handled = False, 0.0, False, False
+        self._guard_exact, self._guard_recorded = False, False
 
     # -- reference API (raft.py:104-148) ------------------------------------
     def freeze_bn(self):
@@ -140,17 +142,19 @@ class RAFT(nn.Module):
             m_ctx, m_fmap = ops.guard_read_now()
             ops.guard_note(self, m_ctx, m_fmap)
             self._guard_handled = True
-            if not (m_fmap < ops.X_LIMIT) or not (m_ctx < float("inf")):
+            # the verdict on the route this forward is about to take (a recorded pass has none but the split one, armed or not)
+            refuse, arm, advice = ops.guard_verdict(m_ctx, m_fmap, self._exact_ctx, fn.recording(cnet))
+            if refuse and advice == ops.GUARD_ADVICE_RECORDED:
+                raise _hip.FocusFlowHipError(
+                    f"RAFT.forward: the context encoder's output reached |x| = {m_ctx:.6g} (limit {ops.X_LIMIT:g}) in a RECORDED pass; the "
+                    "exact-fp32 repair covers inference only.  Train this checkpoint with FF_CONV_PRECISION=fp32.")
+            if refuse and not arm:
                 raise _hip.FocusFlowHipError(
                     f"RAFT.forward: an encoder output reached |x| = {max(m_ctx, m_fmap):.6g}; the fp16-split conv formats need |x| < {ops.X_LIMIT:g} "
                     "(csrc/ff_common.h).  Feature maps beyond it have no local exact route (the correlation values they produce overflow the "
                     "next layer as well), and an infinite context output means a layer INSIDE the encoder overflowed.  Run this checkpoint / "
                     "input with FF_CONV_PRECISION=fp32.")
-            if not (m_ctx < ops.X_LIMIT) and not self._exact_ctx:
-                if fn.recording(cnet):
-                    raise _hip.FocusFlowHipError(
-                        f"RAFT.forward: the context encoder's output reached |x| = {m_ctx:.6g} (limit {ops.X_LIMIT:g}) in a RECORDED pass; the "
-                        "exact-fp32 repair covers inference only.  Train this checkpoint with FF_CONV_PRECISION=fp32.")
+            if arm:       # (nothing has met a split convolution yet: this forward takes the exact route itself)
                 import warnings
                 warnings.warn(f"FF-RAFT: the context encoder's output reached |x| = {m_ctx:.6g} (limit of the fp16-split conv formats: "
                               f"{ops.X_LIMIT:g}); the convolutions that read it run on the exact-fp32 MFMA route from now on")
@@ -212,7 +216,10 @@ class RAFT(nn.Module):
             corr_fn = self._corr_block(fmap1, fmap2, fused_train)
         taped = fn.recording(net, inp)
         # the context features' share of the GRU gate convolutions does not change over the iterations
-        gru_pre = self.update_block.gru.prepare(inp, exact=self._exact_ctx and not taped) if _GRU_CTX_ONCE and (taped or fused_train or not torch.is_grad_enabled()) else None
+        exact = self._exact_ctx and not taped
+        gru_pre = self.update_block.gru.prepare(inp, exact=exact) if _GRU_CTX_ONCE and (taped or fused_train or not torch.is_grad_enabled()) else None
+        # the route this forward takes, for the range guard's look at it afterwards (ops.guard_end)
+        self._guard_exact, self._guard_recorded = exact and gru_pre is not None, taped
         if fused_train:
             lp = train_loop.loop_params(self.update_block)
             pre = [t for zq in gru_pre for t in zq]
