@@ -7,6 +7,9 @@ fp32 tensor (the producer writes what the consumer's loader would have made of t
   * torch.equal against the fp32-input kernel where both run the same matrix instruction (the GRU-epilogue instances of
     conv_patch.hip), 2e-6 relative where the summation order inside a 32-channel chunk differs, 2e-5 against F.conv2d;
   * every tile shape the dispatcher can choose, ragged planes, 1-3 input segments, channel counts off the tile;
+  * the recorded form of the GRU pass (ff_gru_pass_rec, what training runs): the same state bits as the plain form, every gate
+    element stored and nothing else, z / r / q within 2e-5 of fp64, the state the blend of the stored gates to 1e-6; the recorded
+    z IS bit-identical to the z of the two-launch route on the MI355X (both tile heights, both directions, both split formats);
   * the whole forward: split-pair activations on / off give the same flow (1e-4 px; 5e-4 px after 12 iterations at 384 x 512), both within 1e-3 px of the oracle.
 """
 import numpy as np
@@ -214,6 +217,157 @@ def test_gru_pass_as_one_launch_is_bit_identical_to_the_two_convolutions(ops, sh
         z, r = zrd[:, :c], zrd[:, c:]
         q = torch.tanh(F.conv2d(torch.cat([r * hst.double(), mot.double()], 1), wq.double(), bq.cpu().double(), padding=pad) + pre_q.double())
         close(nchw(h1), (1 - z) * hst.double() + z * q, rtol=2e-5, what=f"GRU pass {d + 1} vs fp64")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the RECORDED form of the pass (ff_gru_pass_rec: ops.gru_pass(..., gates=(z, r, q))), what train_loop._forward_fused runs
+REC_SHAPES = [(1, 7, 50), (1, 21, 30), (2, 18, 32), (8, 48, 64)]      # ragged against 4, 6 and 16 twice; 18 = 3 x 6 but not n x 4; the rule's 6
+_REC = {}
+
+
+def _gru_rule(b, h, w):
+    """gru_pass_impl's choice of the tile height, re-derived: rounds of 256 blocks x (rows per tile + 2)."""
+    blocks = {t: b * ((h + t - 1) // t) * ((w + 15) // 16) for t in (4, 6)}
+    cost = {t: (blocks[t] + 255) // 256 * (t + 2) for t in (4, 6)}
+    return (6 if cost[6] <= cost[4] else 4), blocks
+
+
+def _f16_operand(v, s):
+    """What a plain-fp16 product (W_F16: the first term alone) sees of an fp32 value at split scale s."""
+    import split_format_ref as S
+    return S.split(v, s)[0].double() / s
+
+
+def _rec_case(shape, w_fmt):
+    """CPU inputs of both directions and the fp64 z | r of the definition (update.py:45-50) - for W_F16 on the operands that
+    format carries (activations f16(4 v) / 4, weights f16(16 w) / 16: with the fp32 values the format's own rounding, 2^-11 a
+    product, would be what the comparison measures).  Computed once per shape and format, shared by the tile heights."""
+    if (shape, w_fmt) in _REC:
+        return _REC[shape, w_fmt]
+    b, h, w = shape
+    g = torch.Generator().manual_seed(b * 11 + h + w)
+    c = 128
+    x = dict(hst=torch.randn(b, c, h, w, generator=g), mot=torch.randn(b, c, h, w, generator=g),
+             pre_zr=torch.randn(b, 2 * c, h, w, generator=g), pre_q=torch.randn(b, c, h, w, generator=g), dirs=[])
+    op_x = (lambda v: _f16_operand(v, 4.0)) if w_fmt == 2 else (lambda v: v.double())
+    op_w = (lambda v: _f16_operand(v, 16.0)) if w_fmt == 2 else (lambda v: v.double())
+    for kh, kw in ((1, 5), (5, 1)):
+        wzr = torch.randn(2 * c, 2 * c, kh, kw, generator=g) / (2 * c * 5) ** 0.5
+        wq = torch.randn(c, 2 * c, kh, kw, generator=g) / (2 * c * 5) ** 0.5
+        bzr, bq = torch.randn(2 * c, generator=g), torch.randn(c, generator=g)
+        pad = (kh // 2, kw // 2)
+        zr = torch.sigmoid(F.conv2d(torch.cat([op_x(x["hst"]), op_x(x["mot"])], 1), op_w(wzr), bzr.double(), padding=pad) + x["pre_zr"].double())
+
+        def q_of(r_nchw, wq=wq, bq=bq, pad=pad):
+            """fp64 q given r: the definition's own r (fp64) for f16x3; for W_F16 the recorded fp32 r, whose product with h the
+            kernel rounds to fp16 (an fp64 r would round a few of the r h to the neighbouring half)."""
+            rh = op_x(r_nchw.float() * x["hst"]) if w_fmt == 2 else r_nchw.double() * x["hst"].double()
+            return torch.tanh(F.conv2d(torch.cat([rh, op_x(x["mot"])], 1), op_w(wq), bq.double(), padding=pad) + x["pre_q"].double())
+
+        x["dirs"].append(dict(k=(kh, kw), pad=pad, wzr=wzr, wq=wq, bzr=bzr, bq=bq, z=zr[:, :c], r=zr[:, c:], q_of=q_of,
+                              q=q_of(zr[:, c:]) if w_fmt == 1 else None))
+    _REC[shape, w_fmt] = x
+    return x
+
+
+def _gates_buffer(b, h, w, c=128):
+    """z, r, q as channel slices of ONE buffer pre-filled with a value no gate can take: one leading dimension, as
+    ops.gru_pass requires; whatever a launch does not store still holds it (production allocates the stacks with torch.empty)."""
+    buf = torch.full((b, h, w, 3 * c + 8), 3.0e4, device=DEV)
+    return buf, tuple(buf[..., 4 + i * c:4 + (i + 1) * c] for i in range(3))
+
+
+@pytest.mark.parametrize("w_fmt", [1, 2], ids=["f16x3", "f16"])
+@pytest.mark.parametrize("th", [0, 6, 4])
+@pytest.mark.parametrize("shape", REC_SHAPES)
+def test_recorded_gru_pass_stores_the_gates_of_the_state_it_returns(ops, shape, th, w_fmt, monkeypatch):
+    """ff_gru_pass_rec over both tile heights (at 8 x 48 x 64 the product's own rule picks 6: 256 blocks against 384), both
+    directions and both split weight formats:
+      * recording changes nothing: y and y2 are bit-identical to ff_gru_pass on the same inputs;
+      * every element of the three gate slices is stored, nothing outside them is;
+      * z, r, q match fp64 of the definition within the bound the state is held to (close, rtol 2e-5);
+      * z is bit-identical to the z of the two-launch route (zr[..., :128] of the conv_dma.hip launch with the r * h epilogue),
+        as it is on the MI355X in every one of these cases (the same fragments, the same arithmetic in the same order);
+      * the state is consistent with its gates: |y - ((1 - z) h + z q)| < 1e-6, the identity the backward differentiates through
+        (a gate stored on the wrong pixel breaks it by O(1))."""
+    b, h, w = shape
+    if th:
+        monkeypatch.setenv("FF_GRU_PASS_TH", str(th))
+    else:
+        monkeypatch.delenv("FF_GRU_PASS_TH", raising=False)
+    rule, blocks = _gru_rule(b, h, w)
+    if shape == (8, 48, 64):
+        assert (blocks[6], blocks[4], rule) == (256, 384, 6)
+    else:
+        assert rule == 4
+    x = _rec_case(shape, w_fmt)
+    c = 128
+    hp, mp = _views([x["hst"], x["mot"]])
+    hs, ms = ops.split_copy(hp), ops.split_copy(mp)
+    przr, prq = nhwc(x["pre_zr"]), nhwc(x["pre_q"])
+    for d, D in enumerate(x["dirs"]):
+        kh, kw = D["k"]
+        bzr, bq = D["bzr"].to(DEV), D["bq"].to(DEV)
+        pzr, pq = _pack(ops, D["wzr"], 2 * c), _pack(ops, D["wq"], 2 * c)
+        fzr, fq = ops.pack_frag16(pzr, 2 * c), ops.pack_frag16(pq, c)
+        h0, h0s = ops.gru_pass(d, hs, ms, hp, przr, prq, fzr, fq, bzr, bq, w_fmt)
+        buf, (z, r, q) = _gates_buffer(b, h, w)
+        h1, h1s = ops.gru_pass(d, hs, ms, hp, przr, prq, fzr, fq, bzr, bq, w_fmt, gates=(z, r, q))
+        zr2 = ops.conv2d([hs, ms], pzr, bzr, 2 * c, kh, kw, 1, D["pad"], res=przr, act_res=2, w_fmt=w_fmt, ep_rh=hp, ep_split=c, y_split=c, w_frag=fzr)
+        torch.cuda.synchronize()
+        what = f"pass {d + 1}"
+        assert torch.equal(h1, h0), f"{what}: recording changed the new state"
+        assert torch.equal(h1s.t.view(torch.int32), h0s.t.view(torch.int32)), f"{what}: recording changed the new state's split pair"
+        for name, gate in (("z", z), ("r", r), ("q", q)):
+            stale = int((gate == 3.0e4).sum())
+            assert stale == 0, f"{what}: {stale} elements of {name} were never stored"
+        assert bool((buf[..., :4] == 3.0e4).all()) and bool((buf[..., 4 + 3 * c:] == 3.0e4).all()), f"{what}: written outside the gate slices"
+        close(nchw(z), D["z"], rtol=2e-5, what=f"{what}: z vs fp64")
+        close(nchw(r), D["r"], rtol=2e-5, what=f"{what}: r vs fp64")
+        close(nchw(q), D["q"] if w_fmt == 1 else D["q_of"](nchw(r)), rtol=2e-5, what=f"{what}: q vs fp64")
+        same = torch.equal(z, zr2[..., :c])
+        print(f"{shape} th {th} w_fmt {w_fmt} {what}: recorded z bit-identical to the two-launch route: {same}")
+        assert same, f"{what}: z differs from the two-launch route"
+        zd, qd, hd = z.double(), q.double(), hp.double()
+        gap = float((h1.double() - ((1 - zd) * hd + zd * qd)).abs().max())
+        print(f"{shape} th {th} w_fmt {w_fmt} {what}: max |y - ((1 - z) h + z q)| = {gap:.2e}")
+        assert gap < 1e-6, f"{what}: the state is not the blend of the stored gates: {gap:.2e}"
+
+
+def test_recorded_gru_pass_refuses_incomplete_or_misshapen_gate_outputs(ops):
+    """Two of the three gate pointers, a gate leading dimension that is no multiple of 4 or below 128: refused with the
+    entry's message, nothing written."""
+    import re
+    from focusflow_official_amd import _hip
+    b, h, w, c = 1, 7, 20, 128
+    g = torch.Generator().manual_seed(5)
+    hp = torch.randn(b, h, w, c, generator=g).to(DEV)
+    hs = ops.split_copy(hp)
+    przr, prq = torch.zeros(b, h, w, 2 * c, device=DEV), torch.zeros(b, h, w, c, device=DEV)
+    wzr = torch.randn(2 * c, 2 * c, 1, 5, generator=g) / 36
+    fzr = ops.pack_frag16(_pack(ops, wzr, 2 * c), 2 * c)
+    fq = ops.pack_frag16(_pack(ops, wzr[:c].contiguous(), 2 * c), c)
+    bzr = torch.zeros(2 * c, device=DEV)
+    y, y2 = torch.full((b, h, w, c), 3.0e4, device=DEV), torch.full((b, h, w, c), 3.0e4, device=DEV)
+    buf, (z, r, q) = _gates_buffer(b, h, w)
+    p = ops._p
+
+    def rec(z_, r_, q_, gate_ld):
+        _hip.call("ff_gru_pass_rec", 0, p(hs.t), c, p(hs.t), c, p(hp), c, p(przr), 2 * c, p(prq), c, p(fzr), p(fq), p(bzr), p(bzr), 1, p(y), c, p(y2), c,
+                  p(z_), p(r_), p(q_), gate_ld, b, h, w, ops._stream())
+
+    together = "ff_gru_pass_rec: the three gate outputs come together"
+    shape_ = "ff_gru_pass_rec: gate outputs: ld % 4, >= 128, 16-byte aligned"
+    ld = ops._ld(z)
+    for args, message in (((None, r, q, ld), together), ((z, None, q, ld), together), ((z, r, None, ld), together),
+                          ((z, r, q, ld - 2), shape_), ((z, r, q, 124), shape_), ((z[..., 1:], r, q, ld), shape_)):
+        with pytest.raises(_hip.FocusFlowHipError, match=re.escape(message)):
+            rec(*args)
+        torch.cuda.synchronize()
+        assert all(bool((t == 3.0e4).all()) for t in (y, y2, buf)), f"{message}: a refused call wrote"
+    rec(z, r, q, ld)                                          # the same call, complete: runs and stores
+    torch.cuda.synchronize()
+    assert not bool((y == 3.0e4).any()) and not any(bool((t == 3.0e4).any()) for t in (z, r, q))
 
 
 def test_motion_tail_and_split_outputs_of_the_fp32_input_kernels(ops):

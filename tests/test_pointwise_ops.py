@@ -252,12 +252,38 @@ def test_act_bwd_into_a_view(ops, lead, width, pix):
 
 
 @gpu
-@pytest.mark.parametrize("entry", ["act_bwd", "act_bwd_into", "norm_bwd"])
+@pytest.mark.parametrize("entry", ["act_bwd", "act_bwd_into", "norm_bwd", "gru_bwd_blend", "gru_bwd_blend:q", "gru_bwd_rh", "gru_bwd_out"])
 def test_amax_word_only_grows(ops, entry):
     """A word preloaded with a larger value keeps it, one with a smaller positive value grows to the maximum, and an all-zero
-    gradient leaves a zeroed word at 0."""
+    gradient leaves a zeroed word at 0.  (gru_bwd_*: the three producers of csrc/train_ops.hip, called as train_loop.py calls
+    them; the blend step writes two words, g_z's and - ":q" - g_q's.)"""
     dy, y = _act_data((1, 33, 47, 128), R.ACT_SIGMOID, 5)
-    if entry == "norm_bwd":
+    if entry.startswith("gru_bwd"):
+        from focusflow_official_amd import _hip
+        gen = torch.Generator().manual_seed(9)
+        shp, n = (1, 33, 47, 128), 33 * 47
+        z, r = (torch.rand(shp, generator=gen).to(DEV) for _ in range(2))
+        q, h = (torch.tanh(torch.randn(shp, generator=gen)).to(DEV) for _ in range(2))
+        mo = torch.relu(torch.randn(shp, generator=gen)).to(DEV)
+        wide = torch.randn((1, 33, 47, 256), generator=gen).to(DEV)            # [d h | d motion] of an input-gradient convolution
+        p, st = ops._p, ops._stream
+
+        def run(word, zero):
+            up, up2 = (dy.to(DEV) * 0, wide * 0) if zero else (dy.to(DEV), wide)
+            g0, g1, dh, dm = (torch.empty(shp, device=DEV) for _ in range(4))
+            other = torch.zeros(1, dtype=torch.int32, device=DEV)
+            if entry.startswith("gru_bwd_blend"):
+                first = entry == "gru_bwd_blend"
+                _hip.call("ff_gru_bwd_blend", p(up), 128, None, 0, None, 128, p(z), 128, p(q), 128, p(h), 128, p(g0), 128, p(g1), 128, p(dh), 128,
+                          p(word if first else other), p(other if first else word), n, 128, st())
+                return g0 if first else g1
+            if entry == "gru_bwd_rh":
+                dh.copy_(up)
+                _hip.call("ff_gru_bwd_rh", p(up2), 256, p(r), 128, p(h), 128, p(g0), 128, p(dh), 128, p(dm), 128, 1, p(word), n, 128, st())
+            else:
+                _hip.call("ff_gru_bwd_out", p(up), 128, p(up2), 256, p(up), 128, p(mo), 128, p(dh), 128, p(g0), 128, 126, p(word), n, 128, st())
+            return g0
+    elif entry == "norm_bwd":
         case = R.NORM_CASES[0]
         _, per, fixed, x, dyn, res, gamma, beta, st = _norm_run(ops, case, [])
 

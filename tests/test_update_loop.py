@@ -27,6 +27,7 @@ Measured on an MI355X, largest over all tensors of a case, as a fraction of that
   per-iteration lookup backward                          1.25e-5       1.24e-5       7.5e-7
   17x19 planes, b 3, flow_init up to 12 px               3.7e-6        3.8e-6        5.7e-7
   the tape under W_F32                                   -             1.37e-5       -
+  douts x 2^-30 / x 2^20 against x 1 (grads / s; the predictions bit-identical): fused node 5.8e-7 / 6.2e-7, tape 6.9e-7 / 5.2e-7
   W_F16: fused and tape both 7.5e-2 (d fmap1); T = 33 (tape only): fused - tape 1.4e-6
 (The largest fp64 errors are in the predictions and the mask head, where the CPU fp32 oracle shows the same.)
 Seeds: a ReLU output within rounding of zero flips its mask and moves single gradient entries by 1e-3 .. 3e-2 of the
@@ -277,6 +278,29 @@ def test_update_loop_split_formats(raft, det_sd, monkeypatch):
         tape32, route = _run(raft, ins)
     assert route != "UpdateLoopFnBackward"
     _vs_fp64(tape32, r32, r64, keys, "W_F32: tape")
+
+
+def test_update_loop_at_the_gradient_scales_it_trains_at(raft, monkeypatch):
+    """Every dout times 2^-30 (below the 2^-22 an element of a mean loss over a batch of eight 368 x 496 crops carries) and
+    times 2^20: the backward is linear in the douts and the factor a power of two, so grads / s must equal the run at s = 1
+    up to the atomics' summation order - 2e-5 of each tensor's maximum, the module's bound for two routes over identical
+    inputs - and the predictions are the same bits.  Everything between the convolutions' gradient kernels rests on the
+    max|g| words for this: a word that is never written (zero: scale one) or written from the wrong tensor passes at
+    gradients near 2^0 and flushes the split halves to zero, or overflows them, here.  The fused node and the tape."""
+    from focusflow_official_amd import train_loop
+    base = _inputs()
+    preds = [f"flow_up[{t}]" for t in range(base["T"])]
+    gkeys = [k for k in _keys(raft, base["T"]) if k not in preds]
+    for enabled in (True, False):
+        monkeypatch.setattr(train_loop, "ENABLED", enabled)
+        one, route = _run(raft, base)
+        assert (route == "UpdateLoopFnBackward") == enabled, route
+        for e in (-30, 20):
+            s = 2.0 ** e
+            got, _ = _run(raft, dict(base, douts=[d * s for d in base["douts"]]))
+            assert all(torch.equal(got[k], one[k]) for k in preds), f"the predictions depend on the douts (2^{e})"
+            assert all(got.get(k) is not None and bool(torch.isfinite(got[k]).all()) for k in gkeys), f"2^{e}: a gradient is missing or not finite"
+            _vs({k: got[k] / s for k in gkeys}, one, gkeys, f"{'fused node' if enabled else 'tape'}: douts x 2^{e} vs x 1")
 
 
 def test_update_loop_beyond_the_one_launch_lookup_backward(raft, monkeypatch):
